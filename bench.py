@@ -2,6 +2,7 @@
 """Benchmark: ViT-B/16 224x224 bf16 training step (forward + backward + SGD) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model vit_b16] [--batch 256] [--dtype bf16]
+                    [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 Run directly with --gpus N > 1 (no WORLD_SIZE in the environment) it launches the N ranks itself:
@@ -16,10 +17,23 @@ the rendezvous / barrier / max-over-ranks timing and torch.cuda.synchronize(); t
 BEFORE the library so the process has a single HIP runtime.
 
 Prints ONE JSON line (rank 0).  `value` = images/s of the whole job = N*B*K / max-over-ranks
-wall time of the K timed steps.  `roofline` describes the dominant GEMM class, timed with HIP
-events on the stream each kernel runs on, over a second pass of the same K steps (the events
-are kept out of the timed region of `value`).  `cpu_baseline` = the CPU oracle
-(the reference loops restated in C, single thread) timed on this host on a bounded sample.
+wall time of the K timed steps; `ms_per_step` = that wall time / K.  A plain run does only this:
+set up, W warm-up steps, the K timed steps, the line.
+
+--dump-outputs DIR writes (rank 0, after the timed steps) what the last timed step left for the
+caller of ViT.train_step, as float32 DIR/<name>.npy: `loss` (mean_loss of its forward), `logits`
+[B, classes], and `grads` / `params` (after the SGD update) at DUMP_SAMPLE canonical positions
+drawn once from a fixed seed (`sample_index.npy`, float64; every position if the model is
+smaller).  Inputs and parameters are seeded, so two builds run with the same arguments are
+comparable array for array.
+
+--full adds the side measurements (each a pass of its own, outside the timed region):
+`loss_after_warmup` (one extra forward), `roofline` / `kernels` (the dominant GEMM class and the
+per-kernel breakdown, timed with HIP events on the stream each kernel runs on, over a second pass
+of the same K steps with stream concurrency off), `input_pipeline` (the same steps fed by the
+native loader) and `cpu_baseline` (the CPU oracle: the reference loops restated in C, single
+thread, timed on this host on a bounded sample).  --no-timing / --no-pipeline / --no-cpu-baseline
+drop single legs of a --full run.
 """
 import argparse
 import json
@@ -46,6 +60,9 @@ MODEL_NAMES = {"vit_tiny16": "ViT-Tiny/16", "vit_b16": "ViT-B/16", "vit_l16": "V
 FP8_CLASSES = {"gemm_qkv_fwd", "gemm_proj_fwd", "gemm_fc_fwd", "gemm_fcproj_fwd",
                "gemm_qkv_dgrad", "gemm_proj_dgrad", "gemm_fc_dgrad", "gemm_fcproj_dgrad"}
 PEAK_HBM_GBS = 8000.0
+DUMP_SAMPLE = 1 << 21       # --dump-outputs: canonical positions of grads / params kept (8 MiB each,
+                            # 16 MiB of indices: under 64 MB in all with the logits)
+DUMP_SEED = 20240229
 
 
 def pmc_traffic(kernel_class):
@@ -78,10 +95,16 @@ def parse():
                     help="fp8: MXFP8 forward / input-gradient GEMMs (BASELINE config 5)")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--no-overlap", action="store_true", help="one all-reduce after backward")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-timing", action="store_true", help="no per-kernel HIP events")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, logits and a seeded sample of grads / params "
+                         "to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: loss after warm-up, per-kernel timing / roofline "
+                         "pass, input-pipeline rate, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle timing")
+    ap.add_argument("--no-timing", action="store_true", help="--full without the per-kernel HIP events pass")
     ap.add_argument("--no-pipeline", action="store_true",
-                    help="skip the side measurement with the uint8 input pipeline in the loop")
+                    help="--full without the side measurement with the uint8 input pipeline in the loop")
     ap.add_argument("--serial", action="store_true",
                     help="run every pass with stream concurrency off (the profile command of the "
                          "per-kernel roofline pass)")
@@ -263,6 +286,23 @@ def pipeline_rate(m, cfg, B, args):
         os.rmdir(d)
 
 
+def dump_outputs(m, path):
+    """The arrays a caller of train_step can read back after the last timed step -> path/<name>.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = m.num_parameters
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE))
+    else:
+        idx = np.arange(n)
+    loss = float(vit.lib().vit_trainer_mean_loss(m.h))
+    vit.check("mean_loss")
+    np.save(os.path.join(path, "loss.npy"), np.array([loss], np.float32))
+    np.save(os.path.join(path, "logits.npy"), m.logits())
+    np.save(os.path.join(path, "grads.npy"), m.grads()[idx])
+    np.save(os.path.join(path, "params.npy"), m.params()[idx])
+    np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+
+
 def _free_port():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -328,7 +368,8 @@ def main():
     for _ in range(args.warmup):
         m.train_step(args.lr, b_global)
     m.sync()
-    loss_w = m.forward() if args.warmup else float("nan")   # sanity: finite loss after warmup
+    # --full sanity: finite loss after warmup (one extra forward)
+    loss_w = m.forward() if args.full and args.warmup else None
 
     def timed(steps):
         if world > 1:
@@ -352,11 +393,13 @@ def main():
     # the timed region: K plain steps with the production stream concurrency (two micro-batch
     # streams + the weight-gradient stream) and no per-kernel events (~3 % of a step)
     dt = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(m, args.dump_outputs)
     # then the same K steps again, kernels one at a time (concurrency off), with HIP events
     # around every kernel class: the per-kernel breakdown and the roofline of the dominant kernel
     # (durations of kernels that share the GPU with another stream's kernels mean nothing)
     kern = {}
-    if not args.no_timing:
+    if args.full and not args.no_timing:
         m.set_concurrency(False)
         timed(1)
         m.timing_reset()
@@ -367,7 +410,7 @@ def main():
     # side measurement (N=1, not `value`): the same steps fed by the input pipeline — the native
     # loader (pinned ring, background thread) + uint8 H2D upload + device normalise in the loop
     pipe = None
-    if world == 1 and not args.no_pipeline:
+    if args.full and world == 1 and not args.no_pipeline:
         m.set_concurrency(not args.serial)
         pipe = pipeline_rate(m, cfg, B, args)
     ips = world * B * args.steps / dt
@@ -422,7 +465,8 @@ def main():
             **({"mfma_roofline_frac_step_vs_bf16_peak": round(ips * gflop_img / world / (PEAK_BF16_TFLOPS * 1e3), 4)}
                if args.dtype == "fp8" else {}),
             "train_gflop_per_image": round(gflop_img, 3),
-            "loss_after_warmup": round(loss_w, 4),
+            "loss_after_warmup": round(loss_w, 4) if loss_w is not None else None,
+            "full": args.full,
             "roofline": roof, "kernels": ksum,
             **({"roofline_bf16_gemms": roof_bf16, "fp8_gemm_classes": sorted(FP8_CLASSES)} if args.dtype == "fp8" else {}), "input_pipeline": pipe,
             "kernels_note": "per-kernel ms from HIP events over a second pass of the same steps run "
@@ -430,7 +474,7 @@ def main():
                             "split-K then sized for 80 % of the slots instead of the 45 % they use "
                             "beside the micro-batch streams)",
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg)
     elif rank == 0:
         out["cpu_baseline"] = None
