@@ -110,6 +110,18 @@ void gelu_backward(float* dinp, const float* inp, const float* dout, int N);
 /* undefined in the reference, called train_vit.rs:293 (+=): dlogits += (p - 1[tgt]) * dloss */
 void crossentropy_softmax_backward(float* dlogits, const float* dlosses, const float* probs,
                                    const int* targets, int B, int T, int V);
+/* soft-target loss (no reference counterpart; label smoothing / mixup / cutmix).  Row r has the
+ * target distribution t = (1-eps) (lam 1[ta[r]] + (1-lam) 1[tb[r]]) + eps/V; tb NULL = ta.
+ * forward: softmax and loss in one kernel: probs = the bits softmax_forward writes,
+ *          losses[r] = lse(z) - sum_k t_k z_k, from the logits (finite where a probability
+ *          underflows); an out-of-range label gives NaN in that row; losses NULL = softmax_forward.
+ * backward (+=): dlogits += (probs - t) * dlosses[r] */
+void softmax_crossentropy_soft_forward(float* probs, float* losses, const float* logits,
+                                       const int* ta, const int* tb, float lam, float eps,
+                                       int B, int T, int V);
+void crossentropy_soft_softmax_backward(float* dlogits, const float* dlosses, const float* probs,
+                                        const int* ta, const int* tb, float lam, float eps,
+                                        int B, int T, int V);
 /* ViT replacement of encoder_forward (train_vit.rs:196): pixels [B,3,IMG,IMG] ->
  * encoded [B,T,C], row 0 = cls + wpe[0], row 1+p = patch_p . patch_w^T + patch_b + wpe[1+p] */
 void patch_embed_forward(float* encoded, const float* pixels, const float* patch_w,

@@ -43,6 +43,7 @@ typedef struct {
 } vit_config_t;
 
 enum { VIT_FP32 = 0, VIT_BF16 = 1, VIT_FP8 = 2 };
+enum { VIT_MIX_NONE = 0, VIT_MIX_MIXUP = 1, VIT_MIX_CUTMIX = 2 };  /* vit_trainer_mix_batch modes */
 enum { VIT_NUM_PARAM_TENSORS = 20 };
 enum { VIT_MAX_LAYERS = 64 };  /* num_layers range accepted by vit_trainer_create / vit_layout_query */
 
@@ -63,6 +64,26 @@ int vit_trainer_get_grads(vit_trainer_t* t, float* host_grads);
 int vit_trainer_set_batch(vit_trainer_t* t, const float* host_pixels, const int* host_labels);
 /* same from device pointers (stream-ordered device copy) */
 int vit_trainer_set_batch_device(vit_trainer_t* t, const float* dev_pixels, const int* dev_labels);
+/* ---- soft targets: label smoothing, mixup and cutmix on the device batch.  Row r of the loss has
+ *      the target distribution t = (1-eps) (lam 1[labels[r]] + (1-lam) 1[labels[B-1-r]]) + eps/V
+ *      (lam = 1 for an unmixed batch); loss = lse(logits) - t . logits, dlogits = (probs - t) dloss.
+ *      With eps == 0 and no mix the head issues exactly the hard-label launches. ---- */
+/* 0 <= eps < 1 (default 0); persists across batches; a hyper-parameter, not written to checkpoints */
+int vit_trainer_set_label_smoothing(vit_trainer_t* t, float eps);
+/* mix the current device batch in place, image i with image B-1-i (for odd B the middle image is
+ * left as it is); call after any vit_trainer_set_batch* variant; asynchronous on the trainer's
+ * stream.  The batch stays mixed until the next set_batch*.
+ *   VIT_MIX_NONE:   no-op;
+ *   VIT_MIX_MIXUP:  x_i' = lam x_i + (1-lam) x_j with lam in [0,1], every product and the sum
+ *                   rounded to fp32 on its own (no FMA), 1-lam taken in fp32;
+ *   VIT_MIX_CUTMIX: the box [x0,x1) x [y0,y1) (inside the image; may be empty) of all three channel
+ *                   planes is swapped between i and j; the lam argument is ignored and
+ *                   lam = 1 - box_area / img^2 (in double, rounded to float) weighs the labels.
+ * A mix with lam == 1 leaves the targets hard.  Non-zero (with vit_last_error) on a bad argument,
+ * a batch without labels, or a second mix of the same batch; the batch is then left as it was. */
+int vit_trainer_mix_batch(vit_trainer_t* t, int mode, float lam, int x0, int y0, int x1, int y1);
+/* the current device batch [batch,3,img,img] fp32 (mixed or not) to the host; synchronous */
+int vit_trainer_get_pixels(vit_trainer_t* t, float* host);
 /* forward; b_global = global batch of the data-parallel job (dloss = 1/b_global, D15) */
 int vit_trainer_forward(vit_trainer_t* t, int b_global);
 int vit_trainer_zero_grad(vit_trainer_t* t);
@@ -80,11 +101,13 @@ int vit_trainer_get_adamw_state(vit_trainer_t* t, float* m, float* v, int* step)
 /* eval: forward of the current batch, then top-1 per image on the device.
  * host_pred [batch] (nullable) gets the predicted classes (first maximum, as numpy.argmax);
  * host_correct (nullable) gets the number equal to the labels, or -1 when the batch was set
- * without labels.  Synchronous. */
+ * without labels; for a mixed batch these are the batch's own labels (ta), not the partner's.
+ * Synchronous. */
 int vit_trainer_eval(vit_trainer_t* t, int* host_pred, int* host_correct);
 /* zero_grad + forward + backward + step */
 int vit_trainer_train_step(vit_trainer_t* t, float lr, int b_global);
-/* synchronous readbacks; mean_loss = -1 for a batch without labels */
+/* synchronous readbacks; mean_loss = -1 for a batch without labels (the mean of the per-row
+ * soft-target losses when smoothing or a mix is on) */
 float vit_trainer_mean_loss(vit_trainer_t* t);
 int vit_trainer_get_logits(vit_trainer_t* t, float* host_logits); /* [batch, num_classes] */
 int vit_trainer_sync(vit_trainer_t* t);

@@ -20,8 +20,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VIT_LIB") or os.path.join(HERE, "libvit_hip.so")  # VIT_LIB: A/B builds
 
 from . import data  # noqa: E402  (configs, canonical layout, seeded synthetic inputs)
+from . import mix  # noqa: E402  (mixup / cutmix draws and their numpy statement)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
 _lib = None
 
 
@@ -85,6 +87,8 @@ _SIGS = {
     "layernorm_backward": (None, [P, P, P, P, P, P, P, P, I, I, I]),
     "gelu_backward": (None, [P, P, P, I]),
     "crossentropy_softmax_backward": (None, [P, P, P, P, I, I, I]),
+    "softmax_crossentropy_soft_forward": (None, [P, P, P, P, P, F, F, I, I, I]),
+    "crossentropy_soft_softmax_backward": (None, [P, P, P, P, P, F, F, I, I, I]),
     "patch_embed_forward": (None, [P, P, P, P, P, P, I, I, I, I]),
     "patch_embed_backward": (None, [P, P, P, P, P, P, I, I, I, I]),
     "sgd_step": (None, [P, P, LL, F]),
@@ -124,6 +128,9 @@ _SIGS = {
     "vit_trainer_set_params": (I, [P, P]), "vit_trainer_get_params": (I, [P, P]),
     "vit_trainer_get_grads": (I, [P, P]), "vit_trainer_set_batch": (I, [P, P, P]),
     "vit_trainer_set_batch_device": (I, [P, P, P]),
+    "vit_trainer_set_label_smoothing": (I, [P, F]),
+    "vit_trainer_mix_batch": (I, [P, I, F, I, I, I, I]),
+    "vit_trainer_get_pixels": (I, [P, P]),
     "vit_trainer_forward": (I, [P, I]), "vit_trainer_zero_grad": (I, [P]),
     "vit_trainer_backward": (I, [P]), "vit_trainer_step": (I, [P, F]),
     "vit_trainer_train_step": (I, [P, F, I]), "vit_trainer_mean_loss": (F, [P]),
@@ -591,6 +598,22 @@ class ViT:
         sd = np.ascontiguousarray(std, np.float32)
         self._ok(lib().vit_trainer_set_batch_u8(self.h, iptr, lptr, m.ctypes.data_as(P),
                                                 sd.ctypes.data_as(P)), "set_batch_u8")
+
+    def set_label_smoothing(self, eps):
+        """0 <= eps < 1; persists across batches (vit_trainer_set_label_smoothing)."""
+        self._ok(lib().vit_trainer_set_label_smoothing(self.h, float(eps)), "set_label_smoothing")
+
+    def mix_batch(self, mode, lam=1.0, box=None):
+        """Mix the current device batch in place, image i with image B-1-i (vit_trainer_mix_batch):
+        MIX_MIXUP with lam, or MIX_CUTMIX with box = (x0, y0, x1, y1); e.g. *Mixer.draw(img)."""
+        x0, y0, x1, y1 = (int(c) for c in box) if box is not None else (0, 0, 0, 0)
+        self._ok(lib().vit_trainer_mix_batch(self.h, int(mode), float(lam), x0, y0, x1, y1), "mix_batch")
+
+    def pixels(self):
+        """The current device batch [B, 3, img, img] fp32, mixed or not (synchronous)."""
+        out = np.empty((self.B, 3, self.cfg.img, self.cfg.img), dtype=np.float32)
+        self._ok(lib().vit_trainer_get_pixels(self.h, out.ctypes.data_as(P)), "get_pixels")
+        return out
 
     def forward(self, pixels=None, targets=None, b_global=None):
         if pixels is not None:

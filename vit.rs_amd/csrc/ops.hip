@@ -325,9 +325,21 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_k(LnbIo io, const TD* __restri
 
 // ------------------------------------------------------------------ softmax / cross-entropy
 // train_vit.rs:493-517 — block per row, max init -10000 (:499)
+// SOFT: also the soft-target loss of the row, from the logits on the same sweeps:
+//   t = (1-eps) (lam 1[ta] + oml 1[tb]) + eps/V,  loss = lse(z) - t.z = log(s) - t.(z - m)
+// (sum t = 1; s = sum exp(z - m)).  The shifted form keeps the cancellation of lse against z[ta]
+// exact; -sum t log(probs) would be -inf as soon as one probability underflows.  probs are the
+// same bits in both instantiations: the same per-thread strided sums, the same wave / LDS order.
+struct SoftCE {
+    float* losses;
+    const int *ta, *tb;  // tb nullable = ta
+    float lam, oml, eps;
+};
+template <bool SOFT>
 __global__ __launch_bounds__(256) void softmax_k(float* __restrict__ probs,
-                                                 const float* __restrict__ logits, int V) {
+                                                 const float* __restrict__ logits, int V, SoftCE sc) {
     __shared__ float red[4];
+    __shared__ float red2[4];
     const long long row = blockIdx.x;
     const float* l = logits + row * V;
     float* pr = probs + row * V;
@@ -339,18 +351,36 @@ __global__ __launch_bounds__(256) void softmax_k(float* __restrict__ probs,
     __syncthreads();
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     __syncthreads();
-    float s = 0.f;
+    float s = 0.f, sd = 0.f;  // sd: sum of z - m (the eps/V term)
     for (int i = threadIdx.x; i < V; i += 256) {
-        const float e = expf(l[i] - m);
+        const float d = l[i] - m;
+        const float e = expf(d);
         pr[i] = e;
         s += e;
+        if constexpr (SOFT) sd += d;
     }
     s = warp_sum(s);
-    if (lane == 0) red[w] = s;
+    if constexpr (SOFT) sd = warp_sum(sd);
+    if (lane == 0) {
+        red[w] = s;
+        if constexpr (SOFT) red2[w] = sd;
+    }
     __syncthreads();
     s = red[0] + red[1] + red[2] + red[3];
     const float inv = 1.0f / s;
     for (int i = threadIdx.x; i < V; i += 256) pr[i] = pr[i] * inv;
+    if constexpr (SOFT) {
+        if (threadIdx.x == 0) {
+            sd = red2[0] + red2[1] + red2[2] + red2[3];
+            const int a = sc.ta[row], b = sc.tb ? sc.tb[row] : a;
+            float loss = __builtin_nanf("");  // out-of-range labels: NaN, never an OOB read (ce_fwd_k's rule)
+            if (a >= 0 && a < V && b >= 0 && b < V) {
+                const float hard = sc.lam * (l[a] - m) + sc.oml * (l[b] - m);
+                loss = logf(s) - ((1.0f - sc.eps) * hard + (sc.eps / (float)V) * sd);
+            }
+            sc.losses[row] = loss;
+        }
+    }
 }
 __global__ void ce_fwd_k(float* __restrict__ losses, const float* __restrict__ probs,
                          const int* __restrict__ targets, long long rows, int V) {
@@ -369,6 +399,83 @@ __global__ void ce_bwd_k(float* __restrict__ dlogits, const float* __restrict__ 
         const int v = (int)(i - r * V);
         const float ind = v == targets[r] ? 1.0f : 0.0f;
         dlogits[i] += (probs[i] - ind) * dlosses[r];
+    }
+}
+// dlogits += (probs - t) * dloss with the soft target t of softmax_k<true>
+__global__ void ce_soft_bwd_k(float* __restrict__ dlogits, const float* __restrict__ dlosses,
+                              const float* __restrict__ probs, const int* __restrict__ ta,
+                              const int* __restrict__ tb, float lam, float oml, float eps,
+                              long long rows, int V) {
+    const long long n = rows * V;
+    const float base = eps / (float)V, keep = 1.0f - eps;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / V;
+        const int v = (int)(i - r * V);
+        const int a = ta[r], b = tb ? tb[r] : a;
+        const float t = keep * ((v == a ? lam : 0.0f) + (v == b ? oml : 0.0f)) + base;
+        dlogits[i] += (probs[i] - t) * dlosses[r];
+    }
+}
+
+// ------------------------------------------------------------------ batch mixing (mixup / cutmix)
+// In place on pixels [B,3,IMG,IMG]; image i is paired with image B-1-i and one thread owns the same
+// element of both images of a pair (reads both, writes both): race-free, every pixel read once.
+// For odd B the middle image is its own partner and is not touched (lam x + oml x != x in fp32).
+// The blocks of the first grid row also write labels_b[r] = labels[B-1-r].
+// mixup: x_i' = lam x_i + oml x_j, x_j' = lam x_j + oml x_i, each product and sum rounded on its own
+// (no FMA contraction, so a numpy fp32 statement matches bit for bit)
+__device__ __forceinline__ void mix_labels(int* __restrict__ labels_b, const int* __restrict__ labels, int B) {
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < B; t += gridDim.x * blockDim.x)
+        labels_b[t] = labels[B - 1 - t];
+}
+__device__ __forceinline__ float mix1(float a, float b, float lam, float oml) {
+    // plain * and + with contraction off for this block (as sgd_update).  HIP's __fmul_rn /
+    // __fadd_rn do not serve: they are inline * and + in the runtime's header, compiled under the
+    // header's contraction setting, and hipcc fused them into v_pk_fma_f32 (one rounding fewer)
+#pragma clang fp contract(off)
+    return lam * a + oml * b;
+}
+typedef float mixf4 __attribute__((ext_vector_type(4)));
+// blockIdx.y = pair (i, B-1-i), grid-stride over the image's elements (VEC: float4s) along x
+template <bool VEC>
+__global__ void mixup_k(float* __restrict__ px, int* __restrict__ labels_b,
+                        const int* __restrict__ labels, int B, int per, float lam, float oml) {
+    if (blockIdx.y == 0) mix_labels(labels_b, labels, B);
+    const long long oi = (long long)blockIdx.y * per, oj = (long long)(B - 1 - blockIdx.y) * per;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < per; e += gridDim.x * blockDim.x) {
+        if constexpr (VEC) {
+            mixf4* p = reinterpret_cast<mixf4*>(px);
+            const mixf4 a = p[oi + e], b = p[oj + e];
+            mixf4 ra, rb;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                ra[k] = mix1(a[k], b[k], lam, oml);
+                rb[k] = mix1(b[k], a[k], lam, oml);
+            }
+            p[oi + e] = ra;
+            p[oj + e] = rb;
+        } else {
+            const float a = px[oi + e], b = px[oj + e];
+            px[oi + e] = mix1(a, b, lam, oml);
+            px[oj + e] = mix1(b, a, lam, oml);
+        }
+    }
+}
+// cutmix: the box [x0,x1) x [y0,y1) of the three channel planes is swapped between i and B-1-i.
+// Threads run along x (rows of the box stay coalesced); blockIdx.y = (channel, box row),
+// blockIdx.z = pair.
+__global__ void cutmix_k(float* __restrict__ px, int* __restrict__ labels_b,
+                         const int* __restrict__ labels, int B, int IMG, int x0, int y0, int x1, int y1) {
+    if (blockIdx.y == 0 && blockIdx.z == 0) mix_labels(labels_b, labels, B);
+    const int bh = y1 - y0;
+    const int c = blockIdx.y / bh, dy = blockIdx.y - c * bh, i = blockIdx.z;
+    const long long oi = (((long long)i * 3 + c) * IMG + y0 + dy) * IMG;
+    const long long oj = (((long long)(B - 1 - i) * 3 + c) * IMG + y0 + dy) * IMG;
+    for (int x = x0 + blockIdx.x * blockDim.x + threadIdx.x; x < x1; x += gridDim.x * blockDim.x) {
+        const float a = px[oi + x], b = px[oj + x];
+        px[oi + x] = b;
+        px[oj + x] = a;
     }
 }
 
@@ -731,8 +838,16 @@ void sgd(float* p, const float* g, long long n, float lr, hipStream_t s) {
 }
 void softmax_rows(float* probs, const float* logits, long long rows, int V, hipStream_t s) {
     if (rows <= 0) return;
-    softmax_k<<<(unsigned)rows, 256, 0, s>>>(probs, logits, V);
+    softmax_k<false><<<(unsigned)rows, 256, 0, s>>>(probs, logits, V, SoftCE{});
     after_launch("softmax_forward");
+}
+void softmax_ce_soft(float* probs, float* losses, const float* logits, const int* ta, const int* tb,
+                     float lam, float eps, long long rows, int V, hipStream_t s) {
+    if (rows <= 0) return;
+    if (!losses) return softmax_rows(probs, logits, rows, V, s);
+    softmax_k<true><<<(unsigned)rows, 256, 0, s>>>(probs, logits, V,
+                                                    SoftCE{losses, ta, tb, lam, 1.0f - lam, eps});
+    after_launch("softmax_crossentropy_soft_forward");
 }
 void ce_forward(float* losses, const float* probs, const int* targets, long long rows, int V,
                 hipStream_t s) {
@@ -746,7 +861,41 @@ void ce_backward(float* dlogits, const float* dlosses, const float* probs, const
     ce_bwd_k<<<grid_for(rows * V, 256), 256, 0, s>>>(dlogits, dlosses, probs, targets, rows, V);
     after_launch("crossentropy_softmax_backward");
 }
+void ce_soft_backward(float* dlogits, const float* dlosses, const float* probs, const int* ta,
+                      const int* tb, float lam, float eps, long long rows, int V, hipStream_t s) {
+    if (rows <= 0) return;
+    ce_soft_bwd_k<<<grid_for(rows * V, 256), 256, 0, s>>>(dlogits, dlosses, probs, ta, tb, lam,
+                                                          1.0f - lam, eps, rows, V);
+    after_launch("crossentropy_soft_softmax_backward");
+}
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// no pair (B < 2): the image is its own partner
+static void mix_labels_only(int* labels_b, const int* labels, int B, hipStream_t s) {
+    VIT_HIP(hipMemcpyAsync(labels_b, labels, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+}
+void mixup_batch(float* px, int* labels_b, const int* labels, int B, int IMG, float lam, hipStream_t s) {
+    if (B <= 0) return;
+    if (B < 2) return mix_labels_only(labels_b, labels, B, s);
+    const bool vec = (3LL * IMG * IMG) % 4 == 0 && al16(px);
+    const int per = (int)(3LL * IMG * IMG / (vec ? 4 : 1)), pairs = B / 2;
+    // about grid_for's 8192 blocks in all
+    const dim3 grid(std::max(1, std::min(cdiv(per, 256), 8192 / pairs)), pairs);
+    const float oml = 1.0f - lam;
+    if (vec)
+        mixup_k<true><<<grid, 256, 0, s>>>(px, labels_b, labels, B, per, lam, oml);
+    else
+        mixup_k<false><<<grid, 256, 0, s>>>(px, labels_b, labels, B, per, lam, oml);
+    after_launch("mixup_batch");
+}
+void cutmix_batch(float* px, int* labels_b, const int* labels, int B, int IMG, int x0, int y0, int x1,
+                  int y1, hipStream_t s) {
+    if (B <= 0 || x1 <= x0 || y1 <= y0) return;  // an empty box launches nothing
+    if (B < 2) return mix_labels_only(labels_b, labels, B, s);
+    const int bw = x1 - x0, threads = bw > 128 ? 256 : (bw > 64 ? 128 : 64);
+    const dim3 grid(cdiv(bw, threads), 3 * (y1 - y0), B / 2);
+    cutmix_k<<<grid, threads, 0, s>>>(px, labels_b, labels, B, IMG, x0, y0, x1, y1);
+    after_launch("cutmix_batch");
+}
 template <typename TO>
 static void im2col_any(TO* out, const float* px, int B, int IMG, int P, hipStream_t s) {
     const long long n = (long long)B * (IMG / P) * (IMG / P) * 3 * P * P;
@@ -905,6 +1054,15 @@ void softmax_forward(float* probs, const float* logits, int B, int T, int V) {
 void crossentropy_forward(float* losses, const float* probs, const int* targets, int B, int T,
                           int V) {
     ce_forward(losses, probs, targets, (long long)B * T, V, stream());
+}
+void softmax_crossentropy_soft_forward(float* probs, float* losses, const float* logits, const int* ta,
+                                       const int* tb, float lam, float eps, int B, int T, int V) {
+    softmax_ce_soft(probs, losses, logits, ta, tb, lam, eps, (long long)B * T, V, stream());
+}
+void crossentropy_soft_softmax_backward(float* dlogits, const float* dlosses, const float* probs,
+                                        const int* ta, const int* tb, float lam, float eps, int B, int T,
+                                        int V) {
+    ce_soft_backward(dlogits, dlosses, probs, ta, tb, lam, eps, (long long)B * T, V, stream());
 }
 void crossentropy_softmax_backward(float* dlogits, const float* dlosses, const float* probs,
                                    const int* targets, int B, int T, int V) {

@@ -32,6 +32,20 @@ void ce_forward(float* losses, const float* probs, const int* targets, long long
                 hipStream_t s);
 void ce_backward(float* dlogits, const float* dlosses, const float* probs, const int* targets,
                  long long rows, int V, hipStream_t s);
+// soft targets t = (1-eps) (lam 1[ta] + (1-lam) 1[tb]) + eps/V (tb nullable = ta): probs (the bits
+// softmax_rows writes) and losses = lse(z) - t.z in one kernel (losses nullable = softmax_rows);
+// dlogits += (probs - t) * dlosses
+void softmax_ce_soft(float* probs, float* losses, const float* logits, const int* ta, const int* tb,
+                     float lam, float eps, long long rows, int V, hipStream_t s);
+void ce_soft_backward(float* dlogits, const float* dlosses, const float* probs, const int* ta,
+                      const int* tb, float lam, float eps, long long rows, int V, hipStream_t s);
+// batch mixing in place on px [B,3,IMG,IMG], image i with image B-1-i (the middle image of an odd B
+// is left as it is); both also write labels_b[r] = labels[B-1-r] when they launch.
+// mixup: x_i' = rn(rn(lam x_i) + rn((1-lam) x_j));  cutmix: the box [x0,x1) x [y0,y1) of every
+// channel plane is swapped (the caller checks it lies inside the image; an empty box launches nothing)
+void mixup_batch(float* px, int* labels_b, const int* labels, int B, int IMG, float lam, hipStream_t s);
+void cutmix_batch(float* px, int* labels_b, const int* labels, int B, int IMG, int x0, int y0, int x1,
+                  int y1, hipStream_t s);
 void im2col_f32(float* out, const float* px, int B, int IMG, int P, hipStream_t s);
 void im2col_bf16(bf16_t* out, const float* px, int B, int IMG, int P, hipStream_t s);
 // rows padded to KPP columns (zeros past 3*P*P; KPP % 8 == 0): the bf16 GEMM operand of a patch

@@ -267,6 +267,16 @@ struct Trainer {
     float* pixels = nullptr;
     int* labels = nullptr;
     bool has_targets = true;  // false after set_batch without labels: forward only (:264-266)
+    // soft targets: label smoothing (a hyper-parameter: persists, not checkpointed)
+    // and the mix of the current batch (reset by every set_batch*).  labels_b[r] = labels[B-1-r],
+    // allocated by the first mix.  A mix with lam == 1 (an empty cutmix box) changes no pixel and
+    // leaves the targets hard, so the head then runs the launches of an unmixed batch.
+    float smooth_eps = 0.f;
+    bool mixed = false;
+    float mix_lam = 1.f;
+    int* labels_b = nullptr;
+    bool two_labels() const { return mixed && mix_lam != 1.0f; }
+    bool soft_targets() const { return smooth_eps > 0.f || two_labels(); }
     int* preds = nullptr;     // eval: [B] top-1 + one counter
     // uint8 upload: double-buffered device staging filled on s_copy, normalised on s
     hipStream_t s_copy = nullptr;
@@ -1003,8 +1013,13 @@ struct Trainer {
         }
         a.ws = gemm_ws; a.ws_bytes = gemm_ws_bytes;
         gemm_f32(a, s);
-        softmax_rows(probs, logits, B, NC, s);
-        if (has_targets) ce_forward(losses, probs, labels, B, NC, s);
+        if (has_targets && soft_targets()) {
+            softmax_ce_soft(probs, losses, logits, labels, two_labels() ? labels_b : nullptr, mix_lam,
+                            smooth_eps, B, NC, s);
+        } else {
+            softmax_rows(probs, logits, B, NC, s);
+            if (has_targets) ce_forward(losses, probs, labels, B, NC, s);
+        }
         tend();
     }
     // dres_cur (zeroed) <- lnf backward on CLS rows (fp32 dres, or the bf16 stream dres_bf)
@@ -1012,7 +1027,11 @@ struct Trainer {
         tbeg(TC_HEAD, 4.0 * B * C * NC);
         fill_k<<<cdiv(B, 256), 256, 0, s>>>(dlosses, 1.0f / (float)b_global, B);
         VIT_HIP(hipMemsetAsync(dlogits, 0, (size_t)B * NC * 4, s));
-        ce_backward(dlogits, dlosses, probs, labels, B, NC, s);
+        if (soft_targets())
+            ce_soft_backward(dlogits, dlosses, probs, labels, two_labels() ? labels_b : nullptr, mix_lam,
+                             smooth_eps, B, NC, s);
+        else
+            ce_backward(dlogits, dlosses, probs, labels, B, NC, s);
         VIT_HIP(hipMemsetAsync(dlnf, 0, (size_t)B * C * 4, s));
         GemmArgs a;  // dlnf += dlogits . head_w
         a.A = dlogits; a.lda = NC; a.a_kcontig = true;
@@ -1587,6 +1606,7 @@ struct Trainer {
         VIT_HIP(hipEventRecord(u8_copied[k], s_copy));
         VIT_HIP(hipStreamWaitEvent(s, u8_copied[k], 0));
         has_targets = lab != nullptr;
+        mixed = false;
         const long long n = (long long)B * HW;
         normalize_u8_k<<<cdiv(n, 256), 256, 0, s>>>(pixels, labels, u8_stage[k], lab ? lab_stage[k] : nullptr,
                                                      B, HW, mean[0], mean[1], mean[2], sd[0], sd[1], sd[2]);
@@ -1736,6 +1756,7 @@ int vit_trainer_set_batch(vit_trainer_t* h, const float* px, const int* lab) {
     if (lab && !labels_ok(lab, t.B, t.NC)) return 1;
     VIT_HIP(hipMemcpyAsync(t.pixels, px, (size_t)t.B * 3 * t.cfg.img * t.cfg.img * 4, hipMemcpyHostToDevice, t.s));
     t.has_targets = lab != nullptr;
+    t.mixed = false;
     if (lab) VIT_HIP(hipMemcpyAsync(t.labels, lab, (size_t)t.B * 4, hipMemcpyHostToDevice, t.s));
     VIT_HIP(hipStreamSynchronize(t.s));
     return vit::has_error();
@@ -1744,7 +1765,67 @@ int vit_trainer_set_batch_device(vit_trainer_t* h, const float* px, const int* l
     auto& t = h->t;
     VIT_HIP(hipMemcpyAsync(t.pixels, px, (size_t)t.B * 3 * t.cfg.img * t.cfg.img * 4, hipMemcpyDeviceToDevice, t.s));
     t.has_targets = lab != nullptr;
+    t.mixed = false;
     if (lab) VIT_HIP(hipMemcpyAsync(t.labels, lab, (size_t)t.B * 4, hipMemcpyDeviceToDevice, t.s));
+    return vit::has_error();
+}
+int vit_trainer_set_label_smoothing(vit_trainer_t* h, float eps) {
+    if (!h || !(eps >= 0.f && eps < 1.f)) {
+        set_error("vit_trainer_set_label_smoothing: eps %g outside [0, 1)", (double)eps);
+        return 1;
+    }
+    h->t.smooth_eps = eps;
+    return 0;
+}
+int vit_trainer_mix_batch(vit_trainer_t* h, int mode, float lam, int x0, int y0, int x1, int y1) {
+    if (!h) {
+        set_error("vit_trainer_mix_batch: null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    const int img = t.cfg.img;
+    if (mode == VIT_MIX_NONE) return 0;
+    if (mode != VIT_MIX_MIXUP && mode != VIT_MIX_CUTMIX) {
+        set_error("vit_trainer_mix_batch: unknown mode %d", mode);
+        return 1;
+    }
+    if (mode == VIT_MIX_MIXUP && !(lam >= 0.f && lam <= 1.f)) {
+        set_error("vit_trainer_mix_batch: mixup lam %g outside [0, 1]", (double)lam);
+        return 1;
+    }
+    if (mode == VIT_MIX_CUTMIX && (x0 < 0 || y0 < 0 || x1 > img || y1 > img || x0 > x1 || y0 > y1)) {
+        set_error("vit_trainer_mix_batch: box [%d,%d) x [%d,%d) outside the %d x %d image", x0, x1, y0, y1,
+                  img, img);
+        return 1;
+    }
+    if (!t.has_targets) {
+        set_error("vit_trainer_mix_batch: the batch has no labels");
+        return 1;
+    }
+    if (t.mixed) {
+        set_error("vit_trainer_mix_batch: the batch is already mixed");
+        return 1;
+    }
+    if (!t.labels_b) {
+        t.labels_b = t.alloc<int>(t.B);
+        if (!t.labels_b) return 1;
+    }
+    if (mode == VIT_MIX_MIXUP) {
+        vit::mixup_batch(t.pixels, t.labels_b, t.labels, t.B, img, lam, t.s);
+    } else {
+        const double area = (double)(x1 - x0) * (double)(y1 - y0);
+        lam = (float)(1.0 - area / ((double)img * (double)img));
+        vit::cutmix_batch(t.pixels, t.labels_b, t.labels, t.B, img, x0, y0, x1, y1, t.s);
+    }
+    if (vit::has_error()) return 1;
+    t.mixed = true;
+    t.mix_lam = lam;
+    return 0;
+}
+int vit_trainer_get_pixels(vit_trainer_t* h, float* host) {
+    auto& t = h->t;
+    VIT_HIP(hipMemcpyAsync(host, t.pixels, (size_t)t.B * 3 * t.cfg.img * t.cfg.img * 4, hipMemcpyDeviceToHost, t.s));
+    VIT_HIP(hipStreamSynchronize(t.s));
     return vit::has_error();
 }
 int vit_trainer_forward(vit_trainer_t* h, int b_global) {
