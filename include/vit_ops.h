@@ -133,6 +133,12 @@ void patch_embed_backward(float* dpatch_w, float* dpatch_b, float* dcls, float* 
                           int C);
 /* optimizer_step (train_vit.rs:737): params -= lr * grads */
 void sgd_step(float* params, const float* grads, long long n, float lr);
+/* out[0] = sum_i x[i]^2: every square and every sum in double; device pointers; any n >= 0
+ * (n == 0 gives 0).  No reference counterpart: the reduction behind the trainer's global-norm
+ * gradient clipping (vit_trainer_set_grad_clip), which runs this kernel body per gradient chunk.
+ * Deterministic: per-workgroup partial sums (their number a function of n alone) combined in a
+ * fixed order, no floating-point atomics: two calls on the same buffer give the same bits. */
+void grad_sumsq(double* out, const float* x, long long n);
 
 /* ------------------------------------------------------------------ bf16 fast path
  * Build-side extensions with the same conventions; bf16 storage as raw uint16_t, fp32

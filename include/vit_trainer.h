@@ -96,6 +96,26 @@ int vit_trainer_step(vit_trainer_t* t, float lr); /* waits for the all-reduce, t
  *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g g;  p -= lr (m/(1-b1^t) / (sqrt(v/(1-b2^t)) + eps) + wd p) */
 int vit_trainer_step_adamw(vit_trainer_t* t, float lr, float beta1, float beta2, float eps,
                            float weight_decay);
+/* ---- global-norm gradient clipping, for vit_trainer_step, vit_trainer_step_adamw
+ *      and vit_trainer_train_step.  Before the update the device computes S = sum of g^2 over every
+ *      parameter's gradient (every square and sum in double, fixed order: deterministic),
+ *      norm = (float)sqrt(S) and, in fp32 with IEEE division, c = max_norm / (norm + 1e-6f), c = 1
+ *      unless c < 1 (the coefficient of torch.nn.utils.clip_grad_norm_); the optimizer kernels then
+ *      use g' = c * g (rounded to fp32 on its own).  Nothing is read back on the step path.
+ *      c == 1 gives the bits of the unclipped update.
+ *      Unlike torch the gradient arena is NOT scaled: vit_trainer_get_grads keeps returning the raw
+ *      gradients (the all-reduced ones under data parallelism, whose norm is then the one taken,
+ *      identical on every rank).  Non-finite gradients get no special handling: the arithmetic
+ *      above is simply applied (a NaN norm gives c = 1, an infinite one c = 0).
+ *      With clipping on, vit_trainer_train_step does not take the early per-chunk SGD ("early_sgd":
+ *      no parameter may change before the whole norm exists). ---- */
+/* max_norm > 0 (may be +INFINITY: compute the norm, never scale); 0 = off (default).  NaN or a
+ * negative value is an error and leaves the previous setting.  A hyper-parameter: persists across
+ * steps, not written to checkpoints. */
+int vit_trainer_set_grad_clip(vit_trainer_t* t, float max_norm);
+/* global L2 norm of the gradients the last clipped optimizer step used (after the all-reduce under
+ * DP); -1 if no step has computed one.  Synchronous. */
+float vit_trainer_grad_norm(vit_trainer_t* t);
 /* canonical host copies of m, v (either may be NULL) and the step count; synchronous */
 int vit_trainer_get_adamw_state(vit_trainer_t* t, float* m, float* v, int* step);
 /* eval: forward of the current batch, then top-1 per image on the device.
@@ -150,6 +170,10 @@ int vit_trainer_set_concurrency(vit_trainer_t* t, int on);
  *      stream beside the forward; the backward (and every host read) waits for them,
  *      "patch_tail" = 1 (default): bf16 / fp8 modes split the patch embedding's weight gradient for
  *      80 % of the GPU and run its small gradients on a second stream beside it (0: one stream, 45 %),
+ *      "clip_overlap" = -1 (default: auto = 0 in bf16 and fp8 mode, measured): with
+ *      gradient clipping on, bf16 / fp8 and concurrency on, 1 takes each gradient chunk's partial
+ *      sums of squares on the side (all-reduce) stream as soon as the backward has finished the
+ *      chunk, 0 takes them all at step time on the main stream (same bits either way),
  *      "dp_probe" = 1: every gradient chunk is also copied, on the all-reduce stream right after
  *      its all-reduce, into a snapshot arena (read with vit_trainer_get_dp_snapshot) — a check
  *      that each overlapped chunk was final when it was reduced.

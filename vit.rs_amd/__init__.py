@@ -92,6 +92,7 @@ _SIGS = {
     "patch_embed_forward": (None, [P, P, P, P, P, P, I, I, I, I]),
     "patch_embed_backward": (None, [P, P, P, P, P, P, I, I, I, I]),
     "sgd_step": (None, [P, P, LL, F]),
+    "grad_sumsq": (None, [P, P, LL]),
     # bf16 extensions
     "matmul_forward_bf16": (None, [P, P, P, P, I, I, I, I]),
     "matmul_backward_bf16": (None, [P, P, P, P, P, P, I, I, I, I]),
@@ -147,6 +148,7 @@ _SIGS = {
                                ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_double), I]),
     "vit_trainer_step_adamw": (I, [P, F, F, F, F, F]),
     "vit_trainer_get_adamw_state": (I, [P, P, P, ctypes.POINTER(I)]),
+    "vit_trainer_set_grad_clip": (I, [P, F]), "vit_trainer_grad_norm": (F, [P]),
     "vit_trainer_eval": (I, [P, P, ctypes.POINTER(I)]),
     # checkpoints (include/vit_checkpoint.h; host-only)
     "vit_config_num_params": (LL, [ctypes.POINTER(VitConfigC)]),
@@ -639,6 +641,18 @@ class ViT:
         """AdamW (vit_trainer_step_adamw)."""
         self._ok(lib().vit_trainer_step_adamw(self.h, float(lr), float(beta1), float(beta2),
                                               float(eps), float(weight_decay)), "step_adamw")
+
+    def set_grad_clip(self, max_norm):
+        """Global-norm gradient clipping for every later optimizer step: max_norm > 0 (inf: compute
+        the norm, never scale), 0 = off; raises on NaN / negative (vit_trainer_set_grad_clip)."""
+        self._ok(lib().vit_trainer_set_grad_clip(self.h, float(max_norm)), "set_grad_clip")
+
+    def grad_norm(self):
+        """Global L2 norm of the gradients the last clipped step used; -1.0 before any
+        (vit_trainer_grad_norm; synchronous)."""
+        n = float(lib().vit_trainer_grad_norm(self.h))
+        check("grad_norm")
+        return n
 
     def adamw_state(self):
         """(m, v, t) in canonical order."""

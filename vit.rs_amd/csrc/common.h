@@ -160,6 +160,19 @@ __device__ __forceinline__ float sgd_update(float p, float g, float lr) {
     return p - lr * g;
 }
 
+// Global-norm gradient clipping: the device record the finishing kernel writes
+// (sumsq = S in double, norm = (float)sqrt(S), c = min(1, max_norm / (norm + 1e-6f))) and the clipped
+// gradient g' = c * g, rounded to fp32 on its own before sgd_update / adamw_update see it.
+// 1.0f * g == g exactly, so an inactive clip gives the bits of the unclipped update.
+struct ClipRec {
+    double sumsq;
+    float norm, c;
+};
+__device__ __forceinline__ float clip_scale(float c, float g) {
+#pragma clang fp contract(off)
+    return c * g;
+}
+
 // AdamW (oracle ref_adamw_step): one element, every operation rounded like the
 // oracle's line-by-line C (no contraction, correctly rounded sqrt / divide).  omb1 = 1-beta1, omb2 = 1-beta2,
 // bc1/bc2 = the bias corrections 1 - beta^t, computed on the host exactly as the oracle does.

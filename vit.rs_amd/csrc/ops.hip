@@ -52,6 +52,88 @@ __global__ void sgd_k(float* __restrict__ p, const float* __restrict__ g, long l
          i += (long long)gridDim.x * blockDim.x)
         p[i] = sgd_update(p[i], g[i], lr);
 }
+// the same update on g' = c * g, c read from the clip record (clip_scale, common.h)
+__global__ void sgd_clip_k(float* __restrict__ p, const float* __restrict__ g, long long n, float lr,
+                           const ClipRec* __restrict__ rec) {
+    const float c = rec->c;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
+         i += (long long)gridDim.x * blockDim.x)
+        p[i] = sgd_update(p[i], clip_scale(c, g[i]), lr);
+}
+
+// ------------------------------------------------------------------ sum of squares (gradient norm)
+// slots[blockIdx.x] = sum of x[i]^2 over this workgroup's grid-stride share of x[0..n): every element
+// converted to double, squared and added in double (HBM-bound: the double VALU work hides behind the
+// loads; no overflow / underflow of the squares, and the fp32 norm does not depend on the order).
+// 16-byte loads over the aligned body, the unaligned head and the tail as scalars; each thread's
+// elements, the xor-butterfly over the wave and the wave order through LDS are functions of n, the
+// pointer's alignment and the grid (sumsq_blocks(n)) alone: no atomics, the same bits every run.
+constexpr int SUMSQ_THREADS = 256;
+__global__ __launch_bounds__(SUMSQ_THREADS) void sumsq_partial_k(double* __restrict__ slots,
+                                                                 const float* __restrict__ x, long long n) {
+    const long long tid = blockIdx.x * (long long)SUMSQ_THREADS + threadIdx.x;
+    const long long nth = (long long)gridDim.x * SUMSQ_THREADS;
+    long long head = (long long)((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) / 4;
+    if (head > n) head = n;
+    const float4* __restrict__ x4 = reinterpret_cast<const float4*>(x + head);
+    const long long n4 = (n - head) / 4;
+    double acc = 0.0;
+#pragma unroll 4
+    for (long long i = tid; i < n4; i += nth) {
+        const float4 v = x4[i];
+        const double a = (double)v.x, b = (double)v.y, c = (double)v.z, d = (double)v.w;
+        acc += a * a;
+        acc += b * b;
+        acc += c * c;
+        acc += d * d;
+    }
+    // head [0, head) and tail [head + 4 n4, n): at most 3 elements each
+    for (long long i = tid; i < head; i += nth) acc += (double)x[i] * (double)x[i];
+    for (long long i = head + 4 * n4 + tid; i < n; i += nth) acc += (double)x[i] * (double)x[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double wsum[SUMSQ_THREADS / 64];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = wsum[0];
+#pragma unroll
+        for (int w = 1; w < SUMSQ_THREADS / 64; w++) t += wsum[w];
+        slots[blockIdx.x] = t;
+    }
+}
+// One workgroup: S = the slots summed in a fixed order (thread t takes slots t, t + 256, ... in
+// order, then the same butterfly / wave order as above).  CLIP: the clip record {S, norm, c} with
+// norm = (float)sqrt(S) and c = min(1, max_norm / (norm + 1e-6f)) in fp32 with IEEE division
+// (torch.nn.utils.clip_grad_norm_'s coefficient; a NaN c counts as 1); else out[0] = S only.
+template <bool CLIP>
+__global__ __launch_bounds__(SUMSQ_THREADS) void sumsq_finish_k(void* __restrict__ out,
+                                                                const double* __restrict__ slots,
+                                                                int nslots, float max_norm) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nslots; i += SUMSQ_THREADS) acc += slots[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    __shared__ double wsum[SUMSQ_THREADS / 64];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double S = wsum[0];
+#pragma unroll
+    for (int w = 1; w < SUMSQ_THREADS / 64; w++) S += wsum[w];
+    if (CLIP) {
+#pragma clang fp contract(off)
+        ClipRec* r = (ClipRec*)out;
+        const float norm = (float)__builtin_sqrt(S);
+        float c = max_norm / (norm + 1e-6f);
+        if (!(c < 1.0f)) c = 1.0f;
+        r->sumsq = S;
+        r->norm = norm;
+        r->c = c;
+    } else {
+        *(double*)out = S;
+    }
+}
 __global__ void f2bf_k(bf16_t* __restrict__ out, const float* __restrict__ inp, long long n) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x)
@@ -836,6 +918,32 @@ void sgd(float* p, const float* g, long long n, float lr, hipStream_t s) {
     sgd_k<<<grid_for(n, 256), 256, 0, s>>>(p, g, n, lr);
     after_launch("sgd_step");
 }
+void sgd_clip(float* p, const float* g, long long n, float lr, const ClipRec* rec, hipStream_t s) {
+    if (n <= 0) return;
+    sgd_clip_k<<<grid_for(n, 256), 256, 0, s>>>(p, g, n, lr, rec);
+    after_launch("sgd_step_clipped");
+}
+// a function of n alone (not of the device or of anything scheduling-dependent): one workgroup per
+// 4096 elements (four 16-byte loads per thread), at most 1024
+int sumsq_blocks(long long n) {
+    if (n <= 0) return 0;
+    const long long b = (n + 4095) / 4096;
+    return (int)(b > 1024 ? 1024 : b);
+}
+void sumsq_partials(double* slots, const float* x, long long n, hipStream_t s) {
+    const int nb = sumsq_blocks(n);
+    if (!nb) return;
+    sumsq_partial_k<<<nb, SUMSQ_THREADS, 0, s>>>(slots, x, n);
+    after_launch("grad_sumsq_partials");
+}
+void sumsq_finish(double* out, const double* slots, int nslots, hipStream_t s) {
+    sumsq_finish_k<false><<<1, SUMSQ_THREADS, 0, s>>>(out, slots, nslots, 0.f);
+    after_launch("grad_sumsq_finish");
+}
+void clip_finish(ClipRec* rec, const double* slots, int nslots, float max_norm, hipStream_t s) {
+    sumsq_finish_k<true><<<1, SUMSQ_THREADS, 0, s>>>(rec, slots, nslots, max_norm);
+    after_launch("grad_clip_finish");
+}
 void softmax_rows(float* probs, const float* logits, long long rows, int V, hipStream_t s) {
     if (rows <= 0) return;
     softmax_k<false><<<(unsigned)rows, 256, 0, s>>>(probs, logits, V, SoftCE{});
@@ -1110,6 +1218,14 @@ void patch_embed_backward(float* dpatch_w, float* dpatch_b, float* dcls, float* 
 }
 void sgd_step(float* params, const float* grads, long long n, float lr) {
     sgd(params, grads, n, lr, stream());
+}
+void grad_sumsq(double* out, const float* x, long long n) {
+    VIT_REQUIRE(n >= 0, "grad_sumsq: n %lld", n);
+    const int nb = sumsq_blocks(n);
+    double* slots = nb ? (double*)workspace((size_t)nb * sizeof(double)) : nullptr;
+    if (nb && !slots) return;
+    sumsq_partials(slots, x, n, stream());
+    sumsq_finish(out, slots, nb, stream());
 }
 
 // ---------------------------------------------------------------- bf16 extensions

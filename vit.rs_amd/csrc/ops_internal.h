@@ -27,6 +27,16 @@ void ln_backward_bf16_stream(bf16_t* dres_out, uint8_t* lo_out, const bf16_t* dr
 int ln_bwd_blocks(long long rows);
 void convert_f2bf(bf16_t* out, const float* inp, long long n, hipStream_t s);
 void sgd(float* p, const float* g, long long n, float lr, hipStream_t s);
+// p -= lr * (rec->c * g), the product c * g rounded on its own (clip_scale)
+void sgd_clip(float* p, const float* g, long long n, float lr, const ClipRec* rec, hipStream_t s);
+// sum of squares in double, deterministic (the body of grad_sumsq, include/vit_ops.h):
+// sumsq_partials writes sumsq_blocks(n) per-workgroup partial sums (a function of n alone; 0 for
+// n <= 0, then nothing is launched) to slots; sumsq_finish / clip_finish sum nslots of them in slot
+// order with one workgroup into out[0] / into the clip record {S, norm, c} for max_norm
+int sumsq_blocks(long long n);
+void sumsq_partials(double* slots, const float* x, long long n, hipStream_t s);
+void sumsq_finish(double* out, const double* slots, int nslots, hipStream_t s);
+void clip_finish(ClipRec* rec, const double* slots, int nslots, float max_norm, hipStream_t s);
 void softmax_rows(float* probs, const float* logits, long long rows, int V, hipStream_t s);
 void ce_forward(float* losses, const float* probs, const int* targets, long long rows, int V,
                 hipStream_t s);

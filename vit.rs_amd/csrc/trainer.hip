@@ -75,13 +75,20 @@ __global__ void fill_k(float* p, float v, int n) {
     if (i < n) p[i] = v;
 }
 // p -= lr*g; pbf = bf16(p)   (optimizer_step, train_vit.rs:737-743, + bf16 shadow)
-__global__ void sgd_bf16_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                           const float* __restrict__ g, long long n, float lr) {
+// CLIP: g' = c * g (clip_scale: its own rounding) in place of g; the unclipped instantiation is
+// the kernel as it was
+template <bool CLIP>
+__device__ __forceinline__ void sgd_bf16_body(float* __restrict__ p, bf16_t* __restrict__ pbf,
+                                              const float* __restrict__ g, long long n, float lr, float c) {
     const long long n4 = n / 4;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
          i += (long long)gridDim.x * blockDim.x) {
         float4 pv = reinterpret_cast<float4*>(p)[i];
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
+        float4 gv = reinterpret_cast<const float4*>(g)[i];
+        if (CLIP) {
+            gv.x = clip_scale(c, gv.x); gv.y = clip_scale(c, gv.y);
+            gv.z = clip_scale(c, gv.z); gv.w = clip_scale(c, gv.w);
+        }
         pv.x = sgd_update(pv.x, gv.x, lr); pv.y = sgd_update(pv.y, gv.y, lr);
         pv.z = sgd_update(pv.z, gv.z, lr); pv.w = sgd_update(pv.w, gv.w, lr);
         reinterpret_cast<float4*>(p)[i] = pv;
@@ -89,22 +96,39 @@ __global__ void sgd_bf16_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
     }
     for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
-        p[i] = sgd_update(p[i], g[i], lr);
+        p[i] = sgd_update(p[i], CLIP ? clip_scale(c, g[i]) : g[i], lr);
         pbf[i] = f2bf(p[i]);
     }
 }
+__global__ void sgd_bf16_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
+                           const float* __restrict__ g, long long n, float lr) {
+    sgd_bf16_body<false>(p, pbf, g, n, lr, 1.0f);
+}
+__global__ void sgd_bf16_clip_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
+                                const float* __restrict__ g, long long n, float lr,
+                                const ClipRec* __restrict__ rec) {
+    sgd_bf16_body<true>(p, pbf, g, n, lr, rec->c);
+}
 // AdamW over the whole arena (oracle ref_adamw_step), + the bf16 shadow.  One
 // pass: reads p, g, m, v and writes p, m, v (+ pbf) = 7 x 4 B (+2 B) per parameter, HBM-bound.
-__global__ void adamw_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
-                        float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
-                        float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd) {
+// CLIP: as sgd_bf16_body
+template <bool CLIP>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, bf16_t* __restrict__ pbf,
+                                           const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, long long n, float lr, float b1, float b2,
+                                           float omb1, float omb2, float bc1, float bc2, float eps, float wd,
+                                           float c) {
     const long long n4 = n / 4;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
          i += (long long)gridDim.x * blockDim.x) {
         float4 pv = reinterpret_cast<float4*>(p)[i];
-        const float4 gv = reinterpret_cast<const float4*>(g)[i];
+        float4 gv = reinterpret_cast<const float4*>(g)[i];
         float4 mv = reinterpret_cast<float4*>(m)[i];
         float4 vv = reinterpret_cast<float4*>(v)[i];
+        if (CLIP) {
+            gv.x = clip_scale(c, gv.x); gv.y = clip_scale(c, gv.y);
+            gv.z = clip_scale(c, gv.z); gv.w = clip_scale(c, gv.w);
+        }
         pv.x = adamw_update(pv.x, gv.x, mv.x, vv.x, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
         pv.y = adamw_update(pv.y, gv.y, mv.y, vv.y, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
         pv.z = adamw_update(pv.z, gv.z, mv.z, vv.z, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
@@ -117,9 +141,21 @@ __global__ void adamw_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const f
     }
     for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
-        p[i] = adamw_update(p[i], g[i], m[i], v[i], lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
+        p[i] = adamw_update(p[i], CLIP ? clip_scale(c, g[i]) : g[i], m[i], v[i], lr, b1, b2, omb1, omb2, bc1,
+                            bc2, eps, wd);
         if (pbf) pbf[i] = f2bf(p[i]);
     }
+}
+__global__ void adamw_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
+                        float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
+                        float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd) {
+    adamw_body<false>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, 1.0f);
+}
+__global__ void adamw_clip_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
+                             float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
+                             float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd,
+                             const ClipRec* __restrict__ rec) {
+    adamw_body<true>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, rec->c);
 }
 // top-1 of each logits row (first index among equal maxima, as numpy.argmax) and the count of
 // rows whose prediction equals the label (eval path).  One wave per row.
@@ -1533,9 +1569,83 @@ struct Trainer {
         sgd_bf16_k<<<grid_for(n / 4, 256), 256, 0, s_comm>>>(params + o, pbf + o, grads + o, n, early_lr);
         after_launch("sgd_bf16_chunk");
     }
+    // Global-norm gradient clipping (option of vit_trainer_set_grad_clip).  The sum of
+    // squares of the gradients is taken per gradient chunk (the chunk_off ranges, in every mode, so
+    // its bits do not depend on where the launches were issued) into per-workgroup double slots
+    // (ops.hip sumsq_partials), chunk c's at clip_slot_off[c]; the step's finishing kernel sums all
+    // slots in order and writes the clip record {S, norm, c} the clipped optimizer kernels read.
+    // The ranges include the arena's alignment padding, which is zero: init and every
+    // vit_trainer_zero_grad clear the whole arena, every gradient kernel writes G(ti, l) over the
+    // tensor's own extent only, and the all-reduce sums zeros (tests/test_gpu_gradclip.py checks the
+    // norm against the canonical, unpadded gradients).
+    // Overlapped form (bf16 / fp8, concurrency on, timing off, DP overlap on): chunk c's partials run
+    // on s_comm at chunk_done(c), behind the events sgd_chunk / the DP path wait for (and behind the
+    // chunk's all-reduce), beside the rest of the backward; no stream of its own (see early_sgd).
+    // Plain form (otherwise, or when the current backward issued none): all of them at step time on s.
+    float clip_max = 0.f;  // 0 = off
+    int clip_overlap = -1;
+    double* clip_slots = nullptr;  // allocated on first enabling, with clip_rec
+    ClipRec* clip_rec = nullptr;
+    int clip_slot_off[VIT_MAX_LAYERS + 3]{};
+    bool clip_live = false;        // this backward issues the partials on s_comm
+    bool clip_parts_valid = false; // ... and has issued all of them (reset by zero_grad / backward)
+    bool clip_comm_busy = false;   // s_comm may still write clip_slots
+    bool clip_have_norm = false;
+    bool clip_on() const { return clip_max > 0.f; }
+    bool clip_overlap_on() const {
+        if (!(lowp() && two_streams && !timing && s2) || (comm && !overlap)) return false;
+        // auto = the plain form in bf16 and in fp8 mode.  Measured (tools/bench_clip.py, same process,
+        // profiles/grad_clip_ab.txt): ViT-B/16 bf16 SGD plain 36.07 / 36.18 vs overlapped 36.15 / 36.15
+        // ms/step, AdamW 36.35 / 36.45 vs 36.46 / 36.48, ViT-H/14 fp8 119.06 / 118.81 vs 118.89 / 118.91:
+        // no difference outside the 0.1-0.2 ms spread of either, so the form without the
+        // cross-stream events is the default
+        return clip_overlap < 0 ? false : clip_overlap != 0;
+    }
+    bool clip_enable() {
+        if (clip_slots) return true;
+        int n = 0;
+        for (int c = 0; c < n_chunks; c++) {
+            clip_slot_off[c] = n;
+            n += sumsq_blocks(chunk_off[c + 1] - chunk_off[c]);
+        }
+        clip_slot_off[n_chunks] = n;
+        clip_slots = alloc<double>(n);
+        clip_rec = (ClipRec*)alloc<double>(2);
+        return clip_slots && clip_rec;
+    }
+    void clip_partials(int c, hipStream_t st) {
+        sumsq_partials(clip_slots + clip_slot_off[c], grads + chunk_off[c], chunk_off[c + 1] - chunk_off[c], st);
+    }
+    // the clip record of the gradients as they stand (after pre_side_wait and finish_allreduce), on s
+    void clip_norm() {
+        if (clip_comm_busy) {
+            VIT_HIP(hipEventRecord(comm_done, s_comm));
+            VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
+            clip_comm_busy = false;
+        }
+        if (!clip_parts_valid)
+            for (int c = 0; c < n_chunks; c++) clip_partials(c, s);
+        clip_finish(clip_rec, clip_slots, clip_slot_off[n_chunks], clip_max, s);
+        clip_parts_valid = false;
+        clip_have_norm = true;
+    }
     void chunk_done(int c) {
         if (early_on) {
             sgd_chunk(c);
+            return;
+        }
+        if (clip_live && !(comm && overlap)) {  // the events of sgd_chunk, then the chunk's partials
+            VIT_HIP(hipEventRecord(chunk_ev[c], s));
+            VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev[c], 0));
+            VIT_HIP(hipEventRecord(chunk_ev2[c], s2));
+            VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev2[c], 0));
+            for (int k = 1; k < nmb; k++) {
+                hipEvent_t e = chunk_evm[(size_t)c * MAXMB + k];
+                VIT_HIP(hipEventRecord(e, ms[k]));
+                VIT_HIP(hipStreamWaitEvent(s_comm, e, 0));
+            }
+            clip_partials(c, s_comm);
+            clip_comm_busy = true;
             return;
         }
         if (!comm || !overlap) return;
@@ -1555,6 +1665,10 @@ struct Trainer {
         if (r != ncclSuccess) set_error("ncclAllReduce(chunk %d): %s", c, ncclGetErrorString(r));
         if (dp_probe_on)
             VIT_HIP(hipMemcpyAsync(dp_snap + o, grads + o, (size_t)n * 4, hipMemcpyDeviceToDevice, s_comm));
+        if (clip_live) {  // the norm of the reduced gradients: identical on every rank
+            clip_partials(c, s_comm);
+            clip_comm_busy = true;
+        }
     }
     void finish_allreduce() {
         if (!comm) return;  // (world 1 with a communicator still runs RCCL: the tested path)
@@ -1638,10 +1752,18 @@ struct Trainer {
         const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)adam_t);
         const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)adam_t);
         tbeg(TC_SGD, 0);
-        adamw_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(
-            params, lowp() ? pbf : nullptr, grads, adam_m, adam_v, arena_elems, lr,
-            hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay);
-        after_launch("adamw");
+        if (clip_on()) {
+            clip_norm();
+            adamw_clip_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(
+                params, lowp() ? pbf : nullptr, grads, adam_m, adam_v, arena_elems, lr, hp.beta1, hp.beta2,
+                1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay, clip_rec);
+            after_launch("adamw_clipped");
+        } else {
+            adamw_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(
+                params, lowp() ? pbf : nullptr, grads, adam_m, adam_v, arena_elems, lr,
+                hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay);
+            after_launch("adamw");
+        }
         tend();
         if (lowp()) refresh_transposed();
     }
@@ -1657,7 +1779,16 @@ struct Trainer {
         }
         finish_allreduce();
         tbeg(TC_SGD, 0);
-        if (lowp()) {
+        if (clip_on()) {
+            clip_norm();
+            if (lowp()) {
+                sgd_bf16_clip_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(params, pbf, grads, arena_elems, lr,
+                                                                                clip_rec);
+                after_launch("sgd_bf16_clipped");
+            } else {
+                sgd_clip(params, grads, arena_elems, lr, clip_rec, s);
+            }
+        } else if (lowp()) {
             sgd_bf16_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(params, pbf, grads, arena_elems, lr);
             after_launch("sgd_bf16");
         } else {
@@ -1836,6 +1967,7 @@ int vit_trainer_forward(vit_trainer_t* h, int b_global) {
 }
 int vit_trainer_zero_grad(vit_trainer_t* h) {
     auto& t = h->t;
+    t.clip_parts_valid = false;
     // the previous step's all-reduce must be done with the arena before it is cleared
     if (t.comm) {
         VIT_HIP(hipEventRecord(t.comm_done, t.s_comm));
@@ -1856,7 +1988,11 @@ int vit_trainer_backward(vit_trainer_t* h) {
         set_error("vit_trainer_backward: the batch has no targets (forward-only batch)");
         return 1;
     }
+    t.clip_parts_valid = false;
+    t.clip_live = t.clip_on() && !t.early_on && t.clip_overlap_on();
     if (t.lowp()) t.backward_bf16(); else t.backward_f32();
+    t.clip_parts_valid = t.clip_live && !vit::has_error();
+    t.clip_live = false;
     return vit::has_error();
 }
 int vit_trainer_step(vit_trainer_t* h, float lr) {
@@ -1868,7 +2004,9 @@ int vit_trainer_train_step(vit_trainer_t* h, float lr, int b_global) {
     vit_trainer_zero_grad(h);
     vit_trainer_forward(h, b_global);
     // the fused step knows lr before the backward: SGD per finished chunk (Trainer::early_sgd)
-    t.early_on = t.early_sgd_on() && t.lowp() && !t.comm && t.two_streams && !t.timing && t.s2 && t.has_targets;
+    // (not under gradient clipping: no parameter may change before the global norm exists)
+    t.early_on = t.early_sgd_on() && t.lowp() && !t.comm && t.two_streams && !t.timing && t.s2 && t.has_targets &&
+                 !t.clip_on();
     t.early_lr = lr;
     vit_trainer_backward(h);
     t.early_done = t.early_on && !vit::has_error();
@@ -1896,6 +2034,25 @@ int vit_trainer_step_adamw(vit_trainer_t* h, float lr, float beta1, float beta2,
                            float weight_decay) {
     h->t.step_adamw(lr, vit_adamw_t{beta1, beta2, eps, weight_decay});
     return vit::has_error();
+}
+int vit_trainer_set_grad_clip(vit_trainer_t* h, float max_norm) {
+    if (!h || !(max_norm >= 0.f)) {
+        set_error("vit_trainer_set_grad_clip: max_norm %g is not >= 0", (double)max_norm);
+        return 1;
+    }
+    auto& t = h->t;
+    if (max_norm > 0.f && !t.clip_enable()) return 1;
+    if (!(max_norm > 0.f)) t.clip_parts_valid = false;
+    t.clip_max = max_norm;
+    return 0;
+}
+float vit_trainer_grad_norm(vit_trainer_t* h) {
+    auto& t = h->t;
+    if (!t.clip_have_norm) return -1.0f;
+    ClipRec r{};
+    VIT_HIP(hipMemcpyAsync(&r, t.clip_rec, sizeof(r), hipMemcpyDeviceToHost, t.s));
+    VIT_HIP(hipStreamSynchronize(t.s));
+    return r.norm;
 }
 int vit_trainer_get_adamw_state(vit_trainer_t* h, float* m, float* v, int* step) {
     auto& t = h->t;
@@ -2095,6 +2252,8 @@ int vit_trainer_set_option(vit_trainer_t* h, const char* name, int value) {
         t.head_sk = value != 0;
     } else if (n == "fp8_lnb_mx") {  // fp8: the residual-gradient LayerNorm backwards write dres' MX forms (default 1)
         t.lnb_mx = value != 0;
+    } else if (n == "clip_overlap") {  // gradient clipping: partial sums per chunk beside the backward (1), at step time (0), auto (-1)
+        t.clip_overlap = value < 0 ? -1 : value != 0;
     } else if (n == "dp_probe") {
         if (value && !t.dp_snap) {  // allocated once, kept until destroy
             t.dp_snap = t.alloc<float>(t.arena_elems);
