@@ -271,17 +271,17 @@ void gemm_fp8_fused_mxc(void* C, void* C2, long long ldc, const void* aux, long 
                         long long ldb, const float* bias, float* colsum_out, int M, int N, int K, int epi,
                         uint8_t* mx_q, uint8_t* mx_s, uint8_t* mxc_q, uint8_t* mxc_s, long long mxc_ld,
                         long long mxc_off);
-/* tools: GEMM engine selection (0 = the default; 1 = 128x128 everywhere, 2 = 256x256 one tile per
- * workgroup with the split-K weight gradients on 256x128, 4 = 256x128 two per CU everywhere,
- * 5 = 4 with a software-pipelined main loop, 7 = production: 2 with the persistent streaming
- * 256x256 engine for the K-contiguous GEMMs) and diagnostics (flag 2: skip epilogues, main-loop
+/* tools: GEMM engine selection (0 or any other number = the default; 1 = 128x128 everywhere,
+ * 2 = 256x256 one tile per workgroup with the split-K weight gradients on 256x128, 7 = production:
+ * 2 with the persistent streaming 256x256 engine for the K-contiguous GEMMs, 11 = 7 with the
+ * ping-pong 192x256 engine for the shapes it takes) and diagnostics (flag 2: skip epilogues, main-loop
  * timing only; flag 16: the persistent engine drains its stores after each epilogue; flag 32: every
  * output row stored onto row 0 (timing only, wrong outputs: no HBM write traffic); (flags >> 8) &
  * 0xFF: first-round stagger in 0.5 us units; (flags >> 16) & 0xF = g + 1: persistent-engine tile
  * groups of g row panels, 0 = column-major ... default 8 for K <= 768, else row-major) */
 void gemm_bf16_set_variant(int variant);
 void gemm_bf16_set_debug(int flags);
-/* diagnostic: per-workgroup timestamps of the 256x256 / 256x128 bf16 engines into trace (device,
+/* diagnostic: per-workgroup timestamps of the 256x256 bf16 engines into trace (device,
  * 16 x u64 per workgroup of the next launches, 100 MHz s_memrealtime: 0 start, 1 main-loop end,
  * 2 end of wave 0, 3 hardware id = XCC_ID << 32 | HW_ID, 4 + w end of wave w, 12 first K-step's
  * operands landed); NULL turns it off */

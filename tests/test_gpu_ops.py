@@ -4,8 +4,6 @@ fp32 ops: <= 1e-4 relative to the oracle's fp32 result (max-normalised), the par
 BASELINE.json.  bf16 ops: compared with the fp64 oracle run on the bf16-ROUNDED inputs, so only
 accumulation order / output rounding differ; tolerance 1e-2 (bf16 output rounding is 2^-9).
 """
-import os
-
 import numpy as np
 import pytest
 
@@ -359,11 +357,9 @@ def test_error_channel(gpu):
 
 # ------------------------------------------------------------------ generic bf16 GEMM engine
 # The engines the trainer launches (2 = 256x256 one workgroup per CU, with the split-K weight gradients
-# on 256x128; 7 = persistent streaming 256x256; 11 = 7 with the two-group ping-pong 192x256 engine).  The variants that measured
-# slower (4 = 256x128 everywhere, 5 = its software-pipelined form, 9 = one wave per SIMD, 10 = split
-# tail) run only with VIT_TEST_EXPERIMENTAL=1 against a `make EXPERIMENTAL=1` library.
-EXPERIMENTAL = os.environ.get("VIT_TEST_EXPERIMENTAL") == "1"
-ENGINES = [2, 7, 11] + ([4, 5, 9, 10] if EXPERIMENTAL else [])
+# on 256x128; 7 = production: 2 with the persistent streaming 256x256 engine; 11 = 7 with the
+# two-group ping-pong 192x256 engine).
+ENGINES = [2, 7, 11]
 
 
 @pytest.fixture(params=ENGINES)
@@ -437,16 +433,15 @@ def test_gemm_bf16_tile_order_bit_identical(gpu, M, N, K, gm):
         assert np.array_equal(x, y)
 
 
-@pytest.mark.parametrize("pair", [(2, 7), (7, 11)] + ([(4, 5), (2, 9)] if EXPERIMENTAL else []))
+@pytest.mark.parametrize("pair", [(2, 7), (7, 11)])
 @pytest.mark.parametrize("M,N,K", [(6304, 3072, 768), (1576, 768, 3072), (520, 384, 256), (776, 1000, 128),
                                    (50432, 768, 768), (25216, 3072, 768), (25216, 768, 3072), (25216, 768, 2304)])
 def test_gemm_bf16_pipelined_bit_identical(gpu, M, N, K, pair):
-    """Engine variants that reorder only the schedule, not the arithmetic: the software-pipelined
-    256x128 main loop (variant 5, g4::gemm_kernel_pipe) against the 256x128 engine (4), and the
-    persistent streaming 256x256 engine (7, g2::gemm_kernel_s: tiles walked per CU, the next tile's
-    first K-steps fetched under the epilogue, 32-row staging) against the one-tile 256x256 engine
-    (2), and the one-wave-per-SIMD persistent engine (9, g5::gemm_kernel_w4: 128 x 128 per wave, one
-    barrier per 32-deep K-step) against it too.  Same MFMAs in the same K order per accumulator and the same epilogue arithmetic: every
+    """Engine variants that reorder only the schedule, not the arithmetic: the persistent
+    streaming 256x256 engine (7, g2::gemm_kernel_s: tiles walked per CU, the next tile's first
+    K-steps fetched under the epilogue, 32-row staging) against the one-tile 256x256 engine (2),
+    and the two-group ping-pong 192x256 engine (11, gemm_pp.hip) against the streaming engine.
+    Same MFMAs in the same K order per accumulator and the same epilogue arithmetic: every
     fused epilogue of the trainer (bf16 store, GELU pair, fp32 residual, x aux + column sums)
     bit-identical, at the trainer's K (768, 3072), its M (50 432 = 197 full 256-row tiles: several
     tiles per CU) and ragged M / N."""
@@ -496,46 +491,35 @@ def test_gemm_bf16_pipelined_bit_identical(gpu, M, N, K, pair):
         assert pp_hits == (4 if (N % 256 == 0 and M >= 256 and K >= 256) else 0), pp_hits
 
 
-@pytest.mark.parametrize("M,N,K", [(50432, 768, 768), (50432, 768, 3072), (25216, 768, 3072), (25216, 768, 2304),
-                                   (2056, 768, 320), (1000, 520, 128)])
-@pytest.mark.skipif(not EXPERIMENTAL, reason="variant 10 is built with make EXPERIMENTAL=1 only")
-def test_gemm_bf16_tail_split(gpu, M, N, K):
-    """Variant 10: the persistent engine with the last, partly filled round's tiles split along K
-    (fp32 partial tiles + gemm_tail_fix_k) against variant 7 on the same inputs, at the trainer's
-    N = 768 shapes (591 / 297 tiles: a tail of 79 / 41 tiles on 256 CUs) and ragged ones: the bias,
-    fp32-residual and bf16-store epilogues agree to fp32 summation order (the bf16 store to one bf16
-    ulp) over the whole output, and two launches are bitwise equal (fixed part order).  (The
-    full-round tiles are not separately asserted bitwise.)"""
+@pytest.mark.parametrize("retired", [4, 5, 9, 10])
+def test_gemm_bf16_retired_variant_is_default(gpu, retired):
+    """The numbers of the removed engines select nothing: gemm_bf16_set_variant(n) clears the
+    selection like any unknown value, so the GEMM runs on the default engine (7).  At the smallest
+    shape the persistent engine takes (two 256x256 tiles, two K-steps) the bf16-store output is
+    bit-identical to variant 7's and the launch is counted under 256x256, none under 256x128."""
     v = gpu
     L = v.lib()
-    rng = np.random.default_rng(M + 5 * N + K)
-    ab = v.bf16_bits(rng.uniform(-1, 1, size=(M, K)).astype(np.float32))
-    wb = v.bf16_bits((rng.uniform(-1, 1, size=(N, K)) * 0.1).astype(np.float32))
-    A, W = D(v, ab, np.uint16), D(v, wb, np.uint16)
+    M, N, K, epi = 512, 256, 128, 3
+    rng = np.random.default_rng(retired)
+    A = D(v, v.bf16_bits(rng.uniform(-1, 1, size=(M, K)).astype(np.float32)), np.uint16)
+    W = D(v, v.bf16_bits((rng.uniform(-1, 1, size=(N, K)) * 0.1).astype(np.float32)), np.uint16)
     bias = D(v, rng.normal(size=N).astype(np.float32))
-    res = D(v, rng.normal(size=(M, N)).astype(np.float32))
-    outs = {}
+    outs, hits = {}, {}
     try:
-        for var in (7, 10, 10):
+        for var in (7, retired):
             L.gemm_bf16_set_variant(var)
-            o = []
-            for epi in (0, 3, 5):
-                c = Z(v, M * N, np.uint16 if epi == 3 else np.float32)
-                v.call("gemm_bf16_fused", c, None, N, res if epi == 5 else None, N, A, K, 1, W, K, 1, bias,
-                       None, M, N, K, epi)
-                o.append(c.numpy())
-            outs.setdefault(var, []).append(o)
+            v.kernel_hits_reset()
+            c = Z(v, M * N, np.uint16)
+            v.call("gemm_bf16_fused", c, None, N, None, N, A, K, 1, W, K, 1, bias, None, M, N, K, epi)
+            outs[var] = c.numpy()
+            hits[var] = v.kernel_hits()
     finally:
         L.gemm_bf16_set_variant(0)
-    ref, got, again = outs[7][0], outs[10][0], outs[10][1]
-    for e, (x, y, z) in enumerate(zip(ref, got, again)):
-        assert np.array_equal(y, z), e
-        if x.dtype == np.uint16:
-            xf, yf = v.bf16_to_f32(x), v.bf16_to_f32(y)
-            assert np.abs(xf - yf).max() <= 2 ** -7 * np.abs(xf).max(), e
-        else:
-            assert np.abs(x - y).max() <= 1e-5 * np.abs(x).max(), e
-    assert np.abs(ref[2]).max() > 0
+    assert np.abs(v.bf16_to_f32(outs[7])).max() > 0
+    assert np.array_equal(outs[retired], outs[7])
+    for var in (7, retired):
+        assert hits[var][v.HIT_GEMM_256x256 + epi] == 1, var
+        assert hits[var][v.HIT_GEMM_256x128:v.HIT_GEMM_256x128 + 16].sum() == 0, var
 
 
 def _gelu64(x):

@@ -1,6 +1,6 @@
 """Microbenchmark of the bf16 GEMM engines at the trainer's ViT-B/16 B=256 GEMMs (HIP events).
 
-    python tools/bench_gemm.py [--iters 10] [--variants 2,4] [--no-epi]
+    python tools/bench_gemm.py [--iters 10] [--variants 2,7] [--no-epi]
 
 Every GEMM of one transformer layer (forward, dgrad, wgrad) with the epilogue the trainer uses
 (bias, GELU pair, fp32 residual, GELU' with the fused fc-bias column sum, split-K slabs).  Engines
@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--C", type=int, default=768)
-    ap.add_argument("--variants", default="2,4")
+    ap.add_argument("--variants", default="2,7")
     ap.add_argument("--no-epi", action="store_true")
     ap.add_argument("--modes", default=None,  # 256*n: first-round stagger of n s_sleep(127)
                     help="comma-separated gemm_bf16_set_debug flag sets to A/B (2 = no epilogue, "

@@ -1,7 +1,7 @@
 """Per-workgroup timeline of one bf16 GEMM launch (gemm_bf16_set_trace): start, main-loop end and
 end of every workgroup (s_memrealtime, 100 MHz) with its CU, for the trainer's ViT-B/16 B=256 shapes.
 
-    python tools/gemm_trace.py [--variants 2,5] [--only fwd_fc,fwd_qkv] [--stagger 0]
+    python tools/gemm_trace.py [--variants 2,7] [--only fwd_fc,fwd_qkv] [--stagger 0]
 
 Prints per GEMM and engine: launch span, mean main-loop and epilogue time per workgroup, workgroups
 per CU, the share of epilogue time during which the CU's other resident workgroup was in its main
@@ -65,9 +65,9 @@ def analyse(tr, nwaves):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default="2,5")
+    ap.add_argument("--variants", default="2,7")
     ap.add_argument("--only", default="fwd_fc,fwd_qkv,fwd_proj")
-    ap.add_argument("--stagger", type=int, default=0, help="first-round stagger, 0.5 us units (g4 engines)")
+    ap.add_argument("--stagger", type=int, default=0, help="first-round stagger, 0.5 us units (the 256x128 engine)")
     ap.add_argument("--M", type=int, default=0, help="token rows (default 50432; 25216 = one micro-batch)")
     ap.add_argument("--per-round", action="store_true", help="persistent engine: tile times by round")
     ap.add_argument("--debug", default="0", help="comma-separated extra gemm_bf16_set_debug flags to compare "

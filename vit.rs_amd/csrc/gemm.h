@@ -86,10 +86,6 @@ struct GemmArgs {
     uint8_t* mxc_s = nullptr;
     long long mxc_ld = 0;
     long long mxc_off = 0;
-    // variant 10 (split tail of the persistent engine): fp32 partial tiles of the last round, one buffer
-    // per concurrent stream (nullptr = the thread workspace); up to 64 MiB at 256 CUs
-    float* tail_ws = nullptr;
-    size_t tail_ws_bytes = 0;
 };
 
 // fp32 operands, exact-fp32 MFMA (v_mfma_f32_16x16x4_f32); any shape/stride. Parity path.
@@ -98,20 +94,17 @@ void gemm_f32(const GemmArgs& a, hipStream_t s);
 // operands, lda/ldb%8==0, the contiguous dim of an M/N-contig operand %8==0, N%4==0.
 void gemm_bf16(const GemmArgs& a, hipStream_t s);
 bool gemm_bf16_supported(const GemmArgs& a);
-// engine selection for A/B measurements in one process: 1 = 128x128 everywhere, 2 = production
-// (256x256, 1 WG/CU; split-K weight gradients on 256x128, 2 WG/CU), 4 = 256x128 everywhere;
-// anything else = 2.  Debug flag 2 = skip the epilogues (main-loop-only timing).
-// 0 (or any unknown value) clears the selection: the next GEMM re-reads VIT_GEMM (default 7)
+// engine selection for A/B measurements in one process: 1 = 128x128 everywhere, 2 = 256x256, 1 WG/CU,
+// one tile per workgroup (split-K weight gradients on 256x128, 2 WG/CU), 7 = production: as 2 with
+// the persistent streaming 256x256 engine, 11 = as 7 with the ping-pong 192x256 engine for the shapes
+// it takes.  Debug flag 2 = skip the epilogues (main-loop-only timing).
+// 0 (or any other value) clears the selection: the next GEMM re-reads VIT_GEMM (default 7)
 void gemm_set_variant(int v);
 void gemm_set_debug(int flags);
 // compute units of the current device: the persistent engines' grid (one workgroup per CU)
 int gemm_cu_count();
 int gemm_persist_grid();  // workgroups of the persistent engines (VIT_PERSIST_CUS; default gemm_cu_count())
-int gemm_variant_selected();  // the engine variant in effect (VIT_GEMM / gemm_set_variant)
 struct GemmParams;
-// variant 9: the one-wave-per-SIMD persistent engine (gemm_w4.hip) for K-contiguous operands without
-// split-K (K % 64 == 0, K >= 128); false = shape not taken
-bool gemm_bf16_w4(const GemmArgs& a, const GemmParams& p, int tiles, hipStream_t s);
 void gemm_set_trace(unsigned long long* trace);
 // variant 11: the two-group ping-pong engine (gemm_pp.hip, 192x256 tiles) for the shapes it takes
 bool gemm_pp_shape(const GemmArgs& a);

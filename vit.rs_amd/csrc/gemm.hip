@@ -14,7 +14,6 @@
 //   bounds-checked scalar staging; the fp32 parity path.
 #include "gemm_common.h"
 
-#include <algorithm>
 #include <cstdlib>
 
 // one phase per K-step in the persistent engine (the fp8 engine's r06 form): measured slower for bf16
@@ -468,11 +467,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel(GemmParams p) {
 // 1 (so the epilogue's own loads and stores are never waited for by a wait meant for a DMA piece,
 // except in phase 1 of the next tile's second step, when those have long completed).  Same MFMA
 // order per accumulator and the same epilogue arithmetic as gemm_kernel: bit-identical outputs.
-// TS (variant 10): the tiles of the full rounds (p.tfull) as above, then the last round's tiles split
-// into p.tsplit K-ranges of p.kchunk (work items tfull + u * tsplit + part, part-major per tile), each
-// storing its raw fp32 accumulators as a 256x256 partial tile (tpart); gemm_tail_fix_k adds the parts
-// in order and applies the epilogue.  The tail round then keeps every CU busy instead of 1/3 of them.
-template <int EPI, bool TS = false>
+template <int EPI>
 __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(GemmParams p) {
     constexpr int NS = 4;  // DMA two steps ahead
     __shared__ __attribute__((aligned(1024))) char smem[NS * SLOT_BYTES];
@@ -482,8 +477,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(GemmParams p) {
     const int wm = wave >> 2, wn = wave & 3;
     const int ntm = cdiv(p.M, BM), ntn = cdiv(p.N, BN), tiles = ntm * ntn;
     const int nblk = gridDim.x;
-    const int items = TS ? p.tfull + (tiles - p.tfull) * p.tsplit : tiles;
-    const int my_tiles = (items - (int)blockIdx.x + nblk - 1) / nblk;
+    const int my_tiles = (tiles - (int)blockIdx.x + nblk - 1) / nblk;
     const int nk_all = p.K / BK;
     const char* A = (const char*)p.A;
     const char* B = (const char*)p.B;
@@ -499,25 +493,19 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(GemmParams p) {
     first_round_stagger(p.stagger, true);
     // the lane's DMA source of piece j of the A / B image of a tile, as a 32-bit byte offset from
     // the operand base at k = 0 (K-contiguous image: as stage<true>; host: M*lda, N*ldb < 2^31)
+    // kbeg and nk are constants: always 0 and nk_all.  There is no split-K path in this kernel.
+    // They are kept as per-tile fields only to preserve the compiled code: with nk_all used directly
+    // hipcc allocates registers differently in all eight instantiations (bf16 store: 206 VGPRs +
+    // 20 B scratch with the fields, 208 + 0 without; table in profiles/engine_removal_ab.txt).
     struct TileSrc {
-        int tm0, tn0, t, kbeg, nk, part;  // part: index of the partial tile (TS tail items), else -1
+        int tm0, tn0, t, kbeg, nk;
         uint32_t a[2], b[2];
     };
     auto tile_src = [&](int j, TileSrc& ts) {
-        const int it = j * nblk + (int)blockIdx.x;
         ts.kbeg = 0;
         ts.nk = nk_all;
-        ts.part = -1;
-        if (!TS || it < p.tfull) {
-            ts.t = xcd_remap(it, TS ? p.tfull : tiles);
-        } else {
-            const int v = it - p.tfull, u = v / p.tsplit;
-            ts.t = p.tfull + u;
-            ts.part = v;
-            ts.kbeg = (v - u * p.tsplit) * p.kchunk;
-            ts.nk = (min(p.K, ts.kbeg + p.kchunk) - ts.kbeg) / BK;  // host: >= 2 steps
-        }
-        if (!TS && p.gm > 0) {  // (the split-tail variant keeps the row-major order its fix-up assumes)
+        ts.t = xcd_remap(j * nblk + (int)blockIdx.x, tiles);
+        if (p.gm > 0) {
             // groups of gm row panels walked column by column: the tiles an XCD runs at once share
             // gm A panels and 32 / gm B panels instead of ~3 A panels and every B panel
             const int per = p.gm * ntn, g = ts.t / per, r = ts.t - g * per, rows = min(p.gm, ntm - g * p.gm);
@@ -666,19 +654,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(GemmParams p) {
         if (!skip_epilogue(p, acc)) {
             // this tile's last two steps were in slots sl - 1, sl - 2 (mod 4)
             char* stg = smem + ((wave < 4 ? sl + 2 : sl + 3) & 3) * SLOT_BYTES + (wave & 3) * 8192;
-            if (TS && cur.part >= 0) {
-                // raw accumulators into the partial tile in accumulator order (a wave's 32 x 16-B
-                // stores cover whole 1 KiB blocks; no staging, no epilogue registers):
-                // float4 (wave, a, b, lane) at ((wave * 32 + a * 4 + b) * 64 + lane) * 4
-                float* dst = p.tpart + (long long)cur.part * (BM * BN) + wave * 32 * 256 + lane * 4;
-#pragma unroll
-                for (int a = 0; a < 8; a++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) *reinterpret_cast<f32x4_t*>(dst + (a * 4 + b) * 256) = acc[a][b];
-            } else {
-                staged_epilogue_q<EPI>(p, acc, reinterpret_cast<float*>(stg), lane, cur.tm0 + wm * 128,
-                                       cur.tn0 + wn * 64, bpre);
-            }
+            staged_epilogue_q<EPI>(p, acc, reinterpret_cast<float*>(stg), lane, cur.tm0 + wm * 128,
+                                   cur.tn0 + wn * 64, bpre);
         }
         if (p.trace && (tid & 63) == 0) {
             const long long rec = (long long)cur.t * TRACE_WORDS;
@@ -698,41 +675,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(GemmParams p) {
     }
 }
 
-// finish of the split tail (variant 10): tile tfull + u = the sum of its tsplit partial tiles in
-// part order, then the GEMM's epilogue (bias, fp32 residual or bf16 store) as epilogue8 applies it.
-// Block (u, rc): rows 32 rc .. 32 rc + 31 of the tile, thread = (row, 8-column group).
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm_tail_fix_k(GemmParams p) {
-    const int ntn = cdiv(p.N, BN), u = blockIdx.x, t = p.tfull + u;
-    const int tm0 = (t / ntn) * BM, tn0 = (t % ntn) * BN;
-    const int cg = threadIdx.x & 31, r0 = blockIdx.y * 32 + (threadIdx.x >> 5);
-    float cs[8];
-#pragma unroll
-    for (int it = 0; it < 4; it++) {
-        const int r = r0 + it * 8;
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        // (r, 8 cg ..) in the accumulator order of gemm_kernel_s: wave (r / 128) * 4 + c / 64, tile
-        // a = (r % 128) / 16, b = (c % 64) / 16, lane 16 g + r % 16 with g = (c % 16) / 4
-        const int c = cg * 8, wv = (r >> 7) * 4 + (c >> 6), a = (r & 127) >> 4, b = (c & 63) >> 4;
-        const int g = (c & 15) >> 2, i = r & 15;
-        const long long o0 = ((long long)(wv * 32 + a * 4 + b) * 64 + g * 16 + i) * 4, o1 = o0 + 16 * 4;
-        for (int part = 0; part < p.tsplit; part++) {
-            const float* q = p.tpart + ((long long)u * p.tsplit + part) * (BM * BN);
-            const float4 x0 = *reinterpret_cast<const float4*>(q + o0), x1 = *reinterpret_cast<const float4*>(q + o1);
-            v[0] += x0.x; v[1] += x0.y; v[2] += x0.z; v[3] += x0.w;
-            v[4] += x1.x; v[5] += x1.y; v[6] += x1.z; v[7] += x1.w;
-        }
-        const int m = tm0 + r, n = tn0 + cg * 8;
-        if (m >= p.M) continue;
-        if (n + 8 <= p.N) {
-            epilogue8<EPI, false>(p, m, n, v, cs);
-        } else if (n + 4 <= p.N) {
-            f32x4_t w = {v[0], v[1], v[2], v[3]};
-            epilogue<EPI>(p, m, n, w);
-        }
-    }
-}
-
 }  // namespace g2
 
 // ============================================================================ bf16 GEMM, 256x128
@@ -745,6 +687,8 @@ __global__ __launch_bounds__(256) void gemm_tail_fix_k(GemmParams p) {
 // their epilogues at the same moment.  Per K-step: counted vmcnt retires this wave's own pieces
 // of step s (step s+1 stays in flight across the barrier), one raw s_barrier, LDS-DMA of step
 // s+2 into the slot read at step s-1, 12 fragment reads, 32 MFMAs.
+// Only the split-K weight gradients run here (gemm_bf16): A M-contiguous, B N-contiguous, the
+// fp32 slab / accumulate epilogues.
 namespace g4 {
 constexpr int BM = 256, BN = 128, BK = 32, NT = 256;
 constexpr int NSLOT = 3;
@@ -756,8 +700,6 @@ constexpr int PIECES = BM / 64 + BN / 64;      // LDS-DMA instructions per wave 
 static_assert(PIECES == 6, "vmcnt literal below");
 static_assert(NSLOT * SLOT_BYTES >= 4 * STG_WAVE_BYTES, "staged epilogue area");
 
-// K-contig image [R rows][32 k] (64 B rows): 16-B chunk' = chunk ^ ((row >> 1) & 3)
-__device__ __forceinline__ int kc_swz(int row) { return (row >> 1) & 3; }
 // M/N-contig image [32 k][R] (2R-byte rows): chunk' = chunk ^ f(k), f spreading the 8 k rows a
 // 32-lane half of ds_read_b64_tr_b16 touches over distinct 32-B bank groups
 template <int R>
@@ -767,26 +709,18 @@ __device__ __forceinline__ int mn_swz(int k) {
 }
 
 // this wave's R/64 one-KiB pieces of an operand image (piece blk = 4j + wave)
-template <bool KC, int R>
+template <int R>
 __device__ __forceinline__ void stage(const bf16_t* __restrict__ base, long long ld, int row0,
                                       int rows_lim, int k0, char* img, int wave, int lane) {
 #pragma unroll
     for (int j = 0; j < R / 64; j++) {
         const int blk = j * 4 + wave;
-        const bf16_t* src;
-        if constexpr (KC) {
-            const int row = blk * 16 + (lane >> 2);
-            const int c = (lane & 3) ^ kc_swz(row);
-            const int gr = min(row0 + row, rows_lim - 1);
-            src = base + (long long)gr * ld + k0 + c * 8;
-        } else {
-            constexpr int CPR = R / 8;             // 16-B chunks per k row
-            constexpr int KPB = 64 / CPR;          // k rows per piece
-            const int k = blk * KPB + lane / CPR;
-            const int c = (lane % CPR) ^ mn_swz<R>(k);
-            const int gc = min(row0 + c * 8, rows_lim - 8);
-            src = base + (long long)(k0 + k) * ld + gc;
-        }
+        constexpr int CPR = R / 8;     // 16-B chunks per k row
+        constexpr int KPB = 64 / CPR;  // k rows per piece
+        const int k = blk * KPB + lane / CPR;
+        const int c = (lane % CPR) ^ mn_swz<R>(k);
+        const int gc = min(row0 + c * 8, rows_lim - 8);
+        const bf16_t* src = base + (long long)(k0 + k) * ld + gc;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                          (__attribute__((address_space(3))) void*)(img + blk * 1024),
                                          16, 0, 0);
@@ -794,22 +728,17 @@ __device__ __forceinline__ void stage(const bf16_t* __restrict__ base, long long
 }
 
 // 8 bf16 of rows/cols [r0, r0+16) for the slot's 32-deep k: lane (i,g) gets k = 8g + j
-template <bool KC, int R>
+template <int R>
 __device__ __forceinline__ bf16x8_t frag(const char* img, int r0, int lane) {
     const int i = lane & 15, g = lane >> 4;
-    if constexpr (KC) {
-        const int r = r0 + i;
-        return *reinterpret_cast<const bf16x8_t*>(img + r * 64 + ((g ^ kc_swz(r)) << 4));
-    } else {
-        const int q = i >> 2, p = i & 3;
-        const int ch = (r0 >> 3) + (p >> 1);
-        const int k0 = 8 * g + q, k1 = k0 + 4;
-        (void)k1;  // mn_swz<R>(k0 + 4) == mn_swz<R>(k0): a1 = a0 + 4 rows
-        const char* a0 = img + k0 * (2 * R) + ((ch ^ mn_swz<R>(k0)) << 4) + (p & 1) * 8;
-        const bf16x4_t lo = ds_read_tr16_asm<0>(a0);
-        const bf16x4_t hi = ds_read_tr16_asm<4 * 2 * R>(a0);
-        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
+    const int q = i >> 2, p = i & 3;
+    const int ch = (r0 >> 3) + (p >> 1);
+    const int k0 = 8 * g + q, k1 = k0 + 4;
+    (void)k1;  // mn_swz<R>(k0 + 4) == mn_swz<R>(k0): a1 = a0 + 4 rows
+    const char* a0 = img + k0 * (2 * R) + ((ch ^ mn_swz<R>(k0)) << 4) + (p & 1) * 8;
+    const bf16x4_t lo = ds_read_tr16_asm<0>(a0);
+    const bf16x4_t hi = ds_read_tr16_asm<4 * 2 * R>(a0);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // tile order inside the XCD-contiguous range: groups of GM M-tiles walked column by column, so
@@ -825,7 +754,7 @@ __device__ __forceinline__ void group_order(int t, int ntm, int ntn, int& tm, in
     tn = r / gsz;
 }
 
-template <bool AK, bool BKC, int EPI>
+template <int EPI>
 __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(1024))) char smem[NSLOT * SLOT_BYTES];
     first_round_stagger(p.stagger);
@@ -852,8 +781,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmParams p) {
     auto issue = [&](int st) {
         char* sl = smem + (st % NSLOT) * SLOT_BYTES;
         const int k0 = kbeg + st * BK;
-        stage<AK, BM>(A, p.lda, tm0, p.M, k0, sl, wave, lane);
-        stage<BKC, BN>(B, p.ldb, tn0, p.N, k0, sl + A_BYTES, wave, lane);
+        stage<BM>(A, p.lda, tm0, p.M, k0, sl, wave, lane);
+        stage<BN>(B, p.ldb, tn0, p.N, k0, sl + A_BYTES, wave, lane);
     };
     if (nk > 0) issue(0);
     if (nk > 1) issue(1);
@@ -871,14 +800,13 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmParams p) {
         const char* img = smem + (kt % NSLOT) * SLOT_BYTES;
         bf16x8_t fa[8], fb[4];
 #pragma unroll
-        for (int b = 0; b < 4; b++) fb[b] = frag<BKC, BN>(img + A_BYTES, wn * 64 + b * 16, lane);
+        for (int b = 0; b < 4; b++) fb[b] = frag<BN>(img + A_BYTES, wn * 64 + b * 16, lane);
 #pragma unroll
-        for (int a = 0; a < 8; a++) fa[a] = frag<AK, BM>(img, wm * 128 + a * 16, lane);
-        if constexpr (!AK || !BKC) {  // asm transposed reads are not counted by the compiler
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        for (int a = 0; a < 8; a++) fa[a] = frag<BM>(img, wm * 128 + a * 16, lane);
+        // asm transposed reads are not counted by the compiler
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int a = 0; a < 8; a++)
 #pragma unroll
@@ -891,164 +819,6 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmParams p) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     staged_epilogue<EPI>(p, acc, smem + wave * STG_WAVE_BYTES, lane, tm0 + wm * 128, tn0 + wn * 64);
-}
-
-// Software-pipelined form (variant 5; K-contiguous A and B: every forward and input-gradient GEMM
-// of the trainer).  The kernel above reads a K-step's 12 fragments and then issues its 32 MFMAs, so
-// a wave alone on its SIMD leaves the matrix pipe idle for the read latency of every step: it
-// relies on the other resident workgroup's wave to fill those gaps, and while that workgroup runs
-// its epilogue (GELU pair, fp32 residual: up to 40 % of a heavy-epilogue launch) nothing does.
-// Here a wave's reads run under its own MFMAs, so one wave keeps its SIMD's matrix pipe busy and
-// the two workgroups of a CU hide each other's epilogues.  Each K-step is two phases of 16 MFMAs:
-//   phase 0: MFMAs of A rows 0-63 (alo) x B (fb)   ||  reads of A rows 64-127 (ahi) of step s
-//   [vmcnt: own pieces of s+1 landed; lgkmcnt(0); barrier; DMA of step s+3 into slot s % 3]
-//   phase 1: MFMAs of ahi x fb                      ||  reads of fb, alo of step s+1
-// so the fragments in flight cost 16 + 16 VGPRs beyond one step's 48 (two named B sets, the loop
-// unrolled by two).  Ring of 3 slots, DMA three steps ahead.  After step s's barrier every wave
-// has read all of slot s (lgkmcnt(0) before it) and its own pieces of s+1 have landed (s+2's stay
-// in flight: vmcnt(6)), so slot s+1 is readable by all and slot s takes step s+3.  The DMA
-// sources are one 32-bit byte offset per piece from the scalar operand base (6 VGPRs).
-template <int EPI>
-__global__ __launch_bounds__(NT, 2) void gemm_kernel_pipe(GemmParams p) {
-    __shared__ __attribute__((aligned(1024))) char smem[NSLOT * SLOT_BYTES];
-    first_round_stagger(p.stagger);
-    trace_stamp(p, 0);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int ntm = cdiv(p.M, BM), ntn = cdiv(p.N, BN);
-    int tm, tn, wg, split;
-    split_remap(ntm * ntn, wg, split);
-    group_order(wg, ntm, ntn, tm, tn);
-    const int tm0 = tm * BM, tn0 = tn * BN;
-    const int kbeg = split * p.kchunk;
-    const int kend = min(p.K, kbeg + p.kchunk);
-    const int nk = (kend - kbeg) / BK;
-    const char* A = (const char*)p.A;
-    const char* B = (const char*)p.B;
-
-    f32x4_t acc[8][4];
-#pragma unroll
-    for (int a = 0; a < 8; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    // per-piece byte offsets of this lane's 16-B DMA source (K-contig image, as stage<true, R>)
-    uint32_t offa[BM / 64], offb[BN / 64];
-#pragma unroll
-    for (int j = 0; j < BM / 64; j++) {
-        const int row = (j * 4 + wave) * 16 + (lane >> 2);
-        const int c = (lane & 3) ^ kc_swz(row);
-        offa[j] = (uint32_t)(((long long)min(tm0 + row, p.M - 1) * p.lda + c * 8) * 2);
-    }
-#pragma unroll
-    for (int j = 0; j < BN / 64; j++) {
-        const int row = (j * 4 + wave) * 16 + (lane >> 2);
-        const int c = (lane & 3) ^ kc_swz(row);
-        offb[j] = (uint32_t)(((long long)min(tn0 + row, p.N - 1) * p.ldb + c * 8) * 2);
-    }
-    auto issue = [&](int st) {
-        char* sl = smem + (st % NSLOT) * SLOT_BYTES;
-        const long long kb = (long long)(kbeg + st * BK) * 2;
-        const char* a0 = A + kb;
-        const char* b0 = B + kb;
-#pragma unroll
-        for (int j = 0; j < BM / 64; j++)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a0 + offa[j]),
-                                             (__attribute__((address_space(3))) void*)(sl + (j * 4 + wave) * 1024),
-                                             16, 0, 0);
-#pragma unroll
-        for (int j = 0; j < BN / 64; j++)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b0 + offb[j]),
-                                             (__attribute__((address_space(3))) void*)(sl + A_BYTES + (j * 4 + wave) * 1024),
-                                             16, 0, 0);
-    };
-    // fragment reads as inline asm (ds_read_b128, immediate offsets): the compiler neither counts
-    // nor waits for them, the phases below do (hipcc's own counting put lgkmcnt(0) in front of
-    // phase 0, waiting for the reads meant to run under its MFMAs).  Lane (i, g) of a 16-row
-    // fragment at rows r0 + i: kc_swz(r0 + i) = (i >> 1) & 3 for r0 % 16 == 0, so one lane address
-    // per operand and slot, the fragments at + 1 KiB each.
-    const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(char, smem);
-    const uint32_t a_lane = lds0 + (wm * 128 + (lane & 15)) * 64 + (((lane >> 4) ^ kc_swz(lane & 15)) << 4);
-    const uint32_t b_lane = lds0 + A_BYTES + (wn * 64 + (lane & 15)) * 64 + (((lane >> 4) ^ kc_swz(lane & 15)) << 4);
-    auto read_b = [&](int st, bf16x8_t (&fb)[4]) {
-        const uint32_t o = b_lane + (st % NSLOT) * SLOT_BYTES;
-        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\t"
-                     "ds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
-                     : "=&v"(fb[0]), "=&v"(fb[1]), "=&v"(fb[2]), "=&v"(fb[3]) : "v"(o));
-    };
-    auto read_a = [&](int st, int half, bf16x8_t (&fa)[4]) {
-        const uint32_t o = a_lane + (st % NSLOT) * SLOT_BYTES + half * 4096;
-        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\t"
-                     "ds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
-                     : "=&v"(fa[0]), "=&v"(fa[1]), "=&v"(fa[2]), "=&v"(fa[3]) : "v"(o));
-    };
-    auto mfma16 = [&](int half, const bf16x8_t (&fa)[4], const bf16x8_t (&fb)[4]) {
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b < 4; b++)
-                acc[half * 4 + a][b] =
-                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[b], fa[a], acc[half * 4 + a][b], 0, 0, 0);
-    };
-    bf16x8_t alo[4], ahi[4], fbA[4], fbB[4];
-    // step s with B fragments cb (read in the previous step) and the next step's into nb
-    auto step = [&](int s, const bf16x8_t (&cb)[4], bf16x8_t (&nb)[4]) {
-        // phase 0: alo x cb, ahi of step s read underneath (reads issued first)
-        __builtin_amdgcn_sched_barrier(0);
-        read_a(s, 1, ahi);
-        // the 8 reads of the previous phase (cb, alo) are done, this phase's 4 (ahi) stay in flight
-        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(0, alo, cb);
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + 2 < nk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + 3 < nk) issue(s + 3);  // into slot s % 3: every wave has read all of it
-        __builtin_amdgcn_sched_barrier(0);
-        // phase 1: ahi x cb, step s+1's fb and alo read underneath (unconditionally: past the
-        // last step the slot holds stale data nobody uses and no DMA writes it, and straight-line
-        // reads keep the compiler's lgkmcnt tracking exact)
-        read_b(s + 1, nb);
-        read_a(s + 1, 0, alo);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma16(1, ahi, cb);  // ahi: retired by the lgkmcnt(0) in front of the barrier
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
-    if (nk > 0) {
-        issue(0);
-        if (nk > 1) issue(1);
-        if (nk > 2) issue(2);
-        // own pieces of step 0 landed (1 and 2 stay in flight), then fb, alo of step 0
-        __builtin_amdgcn_sched_barrier(0);
-        if (nk > 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (nk > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        trace_stamp(p, 12);
-        read_b(0, fbA);
-        read_a(0, 0, alo);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    for (int kt = 0; kt < nk; kt += 2) {  // nk is even (host: K and the split chunk % 64 == 0)
-        step(kt, fbA, fbB);
-        step(kt + 1, fbB, fbA);
-    }
-    trace_stamp(p, 1);
-
-    if (skip_epilogue(p, acc)) return;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    staged_epilogue<EPI>(p, acc, smem + wave * STG_WAVE_BYTES, lane, tm0 + wm * 128, tn0 + wn * 64);
-    trace_stamp(p, 2);
 }
 }  // namespace g4
 
@@ -1326,21 +1096,14 @@ __global__ __launch_bounds__(256) void slab_reduce_k(float* __restrict__ C, long
 
 // engine selection (gemm_bf16_set_variant; default from VIT_GEMM, else 7):
 //   1 = 128x128 register-staged everywhere, 2 = 256x256 one workgroup per CU (one tile per
-//   workgroup; split-K weight gradients on 256x128), 4 = 256x128 two per CU everywhere, 5 = as 4
-//   with the software-pipelined main loop (g4::gemm_kernel_pipe) for K-contiguous operands,
-//   7 = production: as 2 with the persistent streaming 256x256 engine (g2::gemm_kernel_s) for the
-//   K-contiguous GEMMs without split-K, 11 = as 7 with the two-group ping-pong
-//   192x256 engine (gemm_pp.hip) for the shapes it takes.  Debug flag 2 skips the
-//   epilogues (main-loop-only timing; results are garbage).
+//   workgroup; split-K weight gradients on 256x128), 7 = production: as 2 with the persistent
+//   streaming 256x256 engine (g2::gemm_kernel_s) for the K-contiguous GEMMs without split-K
+//   (DESIGN.md §4.6), 11 = as 7 with the two-group ping-pong 192x256 engine (gemm_pp.hip) for the
+//   shapes it takes.  Debug flag 2 skips the epilogues (main-loop-only timing;
+//   results are garbage).
 static int g_variant = -1;
 static int g_debug_flags = 0;
-// variants 5 (software-pipelined 256x128), 9 (one wave per SIMD, gemm_w4.hip) and 10 (split tail) measured
-// slower than 7 and are built only with `make EXPERIMENTAL=1`
-#if VIT_GEMM_EXPERIMENTAL
-static bool known_variant(int v) { return v == 1 || v == 2 || v == 4 || v == 5 || v == 7 || v == 9 || v == 10 || v == 11; }
-#else
-static bool known_variant(int v) { return v == 1 || v == 2 || v == 4 || v == 7 || v == 11; }
-#endif
+static bool known_variant(int v) { return v == 1 || v == 2 || v == 7 || v == 11; }
 static constexpr int kDefaultVariant = 7;
 static int gemm_variant() {
     if (g_variant < 0) {
@@ -1371,8 +1134,7 @@ int gemm_persist_grid() {
     }();
     return n;
 }
-int gemm_variant_selected() { return gemm_variant(); }
-bool gemm_streaming() { return gemm_variant() == 7 || gemm_variant() == 9 || gemm_variant() == 10 || gemm_variant() == 11; }
+bool gemm_streaming() { return gemm_variant() == 7 || gemm_variant() == 11; }
 void gemm_set_debug(int flags) { g_debug_flags = flags; }
 static int g_debug_flags_fwd() { return g_debug_flags; }
 static unsigned long long* g_trace = nullptr;
@@ -1407,9 +1169,6 @@ GemmParams make_gemm_params(const GemmArgs& a, int kchunk) {
     p.mxc_off = (int)a.mxc_off;
     p.mxc_rg = (int)(mx_rows_padded(a.N) / 32);
     p.tiles = 1;
-    p.tsplit = 0;
-    p.tfull = 0;
-    p.tpart = nullptr;
     return p;
 }
 
@@ -1524,50 +1283,9 @@ static void launch_bf16(const GemmArgs& a, const GemmParams& p, dim3 grid, hipSt
 template <bool AK, bool BKC>
 static void launch_g2(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStream_t s) {
     if constexpr (AK && BKC) {
-#if VIT_GEMM_EXPERIMENTAL
-        // one-wave-per-SIMD persistent engine (gemm_w4.hip)
-        if (gemm_variant() == 9 && grid.y == 1 && gemm_bf16_w4(a, p, (int)grid.x, s)) return;
-        // persistent streaming engine with a split tail (variant 10): when the last round fills at
-        // most half the CUs, its tiles run as K-ranges on all of them (bias / residual / bf16 store
-        // epilogues; fp32 partial tiles in a.tail_ws or the thread workspace + gemm_tail_fix_k)
-        if (gemm_variant() == 10 && a.tail_ws && grid.y == 1 && p.K >= 2 * g2::BK && p.kchunk == p.K &&
-            (a.epi == EPI_F32_STORE || a.epi == EPI_BF16_STORE || a.epi == EPI_F32_RESID) &&
-            (long long)p.M * p.lda * 2 < (1LL << 31) && (long long)p.N * p.ldb * 2 < (1LL << 31)) {
-            const int cus = gemm_cu_count(), tiles = (int)grid.x;
-            const int nblk = tiles < cus ? tiles : cus, full = tiles / nblk * nblk, tail = tiles - full;
-            const int nk = p.K / g2::BK;
-            int split = tail > 0 && full > 0 ? std::min(nblk / tail, nk / 2) : 1;
-            if (split >= 2) {
-                const int kchunk = cdiv(cdiv(p.K, split), 2 * g2::BK) * (2 * g2::BK);  // even step count
-                split = cdiv(p.K, kchunk);
-                const size_t need = (size_t)tail * split * g2::BM * g2::BN * sizeof(float);
-                // the caller's per-stream buffer only: the thread workspace is shared by concurrent streams
-                float* part = a.tail_ws_bytes >= need ? a.tail_ws : nullptr;
-                if (split >= 2 && part) {
-                    GemmParams q = p;
-                    q.tsplit = split;
-                    q.tfull = full;
-                    q.kchunk = kchunk;
-                    q.tpart = part;
-                    switch (a.epi) {
-#define VIT_CASE(E)                                                                   \
-    case E:                                                                           \
-        g2::gemm_kernel_s<E, true><<<nblk, g2::NT, 0, s>>>(q);                         \
-        g2::gemm_tail_fix_k<E><<<dim3(tail, g2::BM / 32), 256, 0, s>>>(q);            \
-        return;
-                        VIT_CASE(EPI_F32_STORE)
-                        VIT_CASE(EPI_BF16_STORE)
-                        VIT_CASE(EPI_F32_RESID)
-#undef VIT_CASE
-                        default: break;
-                    }
-                }
-            }
-        }
-#endif
         // persistent streaming engine: one workgroup per CU (at most one per tile), no split-K;
         // its DMA ring runs two K-steps ahead across one tile boundary, so K >= 2 steps
-        if ((gemm_variant() == 7 || gemm_variant() == 10 || gemm_variant() == 11) && grid.y == 1 && p.K >= 2 * g2::BK &&
+        if ((gemm_variant() == 7 || gemm_variant() == 11) && grid.y == 1 && p.K >= 2 * g2::BK &&
             (long long)p.M * p.lda * 2 < (1LL << 31) &&
             (long long)p.N * p.ldb * 2 < (1LL << 31)) {
             const int cus = gemm_persist_grid();
@@ -1591,52 +1309,6 @@ static void launch_g2(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStre
     switch (a.epi) {
 #define VIT_CASE(E) \
     case E: g2::gemm_kernel<AK, BKC, E, 2><<<grid, g2::NT, 0, s>>>(p); break;
-        VIT_CASE(EPI_F32_STORE)
-        VIT_CASE(EPI_F32_ACC)
-        VIT_CASE(EPI_BF16_STORE)
-        VIT_CASE(EPI_BF16_GELU)
-        VIT_CASE(EPI_F32_RESID)
-        VIT_CASE(EPI_BF16_DGELU)
-        VIT_CASE(EPI_F32_SLAB)
-        VIT_CASE(EPI_BF16_GELU_D)
-        VIT_CASE(EPI_BF16_MUL)
-#undef VIT_CASE
-        default: set_error("gemm_bf16: unsupported epilogue %d", a.epi); return;
-    }
-}
-
-
-template <bool AK, bool BKC>
-static void launch_g4(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStream_t s) {
-    if constexpr (AK && BKC) {
-        // software-pipelined main loop: an even step count per split and 32-bit DMA offsets
-        const bool fits = p.kchunk % 64 == 0 && p.K % 64 == 0 && (long long)p.M * p.lda * 2 < (1LL << 32) &&
-                          (long long)p.N * p.ldb * 2 < (1LL << 32);
-#if VIT_GEMM_EXPERIMENTAL
-        if (gemm_variant() == 5 && fits) {
-            switch (a.epi) {
-#define VIT_CASE(E) \
-    case E: g4::gemm_kernel_pipe<E><<<grid, g4::NT, 0, s>>>(p); return;
-                VIT_CASE(EPI_F32_STORE)
-                VIT_CASE(EPI_F32_ACC)
-                VIT_CASE(EPI_BF16_STORE)
-                VIT_CASE(EPI_BF16_GELU)
-                VIT_CASE(EPI_F32_RESID)
-                VIT_CASE(EPI_BF16_DGELU)
-                VIT_CASE(EPI_F32_SLAB)
-                VIT_CASE(EPI_BF16_GELU_D)
-                VIT_CASE(EPI_BF16_MUL)
-#undef VIT_CASE
-                default: break;
-            }
-        }
-#else
-        (void)fits;
-#endif
-    }
-    switch (a.epi) {
-#define VIT_CASE(E) \
-    case E: g4::gemm_kernel<AK, BKC, E><<<grid, g4::NT, 0, s>>>(p); break;
         VIT_CASE(EPI_F32_STORE)
         VIT_CASE(EPI_F32_ACC)
         VIT_CASE(EPI_BF16_STORE)
@@ -1694,43 +1366,35 @@ static int choose_split_g4(int tiles, int nk, int fill_pct = 0) {
     return best;
 }
 
+// a split-K weight gradient (EPI_F32_ATOMIC, M-contiguous A, N-contiguous B) on the 256x128 engine
 static void gemm_bf16_g4(const GemmArgs& a, hipStream_t s) {
     const int tiles = cdiv(a.M, g4::BM) * cdiv(a.N, g4::BN);
-    int split = 1;
-    if (a.epi == EPI_F32_ATOMIC) split = a.splitk > 0 ? a.splitk : choose_split_g4(tiles, a.K / g4::KTILE, a.fill_pct);
+    int split = a.splitk > 0 ? a.splitk : choose_split_g4(tiles, a.K / g4::KTILE, a.fill_pct);
     int kchunk = cdiv(cdiv(a.K, split), g4::KTILE) * g4::KTILE;
     split = cdiv(a.K, kchunk);
     GemmArgs b = a;
     float* slab = nullptr;
-    if (a.epi == EPI_F32_ATOMIC) {
-        // split-K partials go to fp32 slabs + one reduce (no float atomics in the GEMM); a single
-        // split accumulates in place
-        if (split > 1) {
-            if (!(slab = slab_buffer(a, split))) return;
-            b.epi = EPI_F32_SLAB;
-            b.C = slab;
-            b.ldc = a.N;
-        } else {
-            b.epi = EPI_F32_ACC;
-        }
+    // split-K partials go to fp32 slabs + one reduce (no float atomics in the GEMM); a single
+    // split accumulates in place
+    if (split > 1) {
+        if (!(slab = slab_buffer(a, split))) return;
+        b.epi = EPI_F32_SLAB;
+        b.C = slab;
+        b.ldc = a.N;
+    } else {
+        b.epi = EPI_F32_ACC;
     }
     GemmParams p = make_gemm_params(b, kchunk);
     p.tiles = tiles;
-    float* cs_rows = colsum_rows_begin(a);
-    if ((a.colsum_out || a.colsum_part) && epi_aux16(a.epi) && !cs_rows) return;
-    p.colsum_out = cs_rows;
     dim3 grid(tiles, split);
-    if (a.a_kcontig && a.b_kcontig) launch_g4<true, true>(b, p, grid, s);
-    else if (a.a_kcontig && !a.b_kcontig) launch_g4<true, false>(b, p, grid, s);
-    else if (!a.a_kcontig && !a.b_kcontig) launch_g4<false, false>(b, p, grid, s);
-    else launch_g4<false, true>(b, p, grid, s);
+    if (slab) g4::gemm_kernel<EPI_F32_SLAB><<<grid, g4::NT, 0, s>>>(p);
+    else g4::gemm_kernel<EPI_F32_ACC><<<grid, g4::NT, 0, s>>>(p);
     after_launch("gemm_bf16_256x128");
     count_hit(VIT_HIT_GEMM_256x128 + b.epi);
     if (slab) slab_reduce(a, slab, split, s);
-    colsum_rows_end(a, cs_rows, s);
-    // bias gradient of a wgrad (M-contig A = dout^T): column sums of dout over the K rows (the
-    // thread workspace may be the slab just reduced: stream-ordered after the reduce)
-    if (a.dbias && !a.a_kcontig) colsum_bf16(a.dbias, (const bf16_t*)a.A, a.K, a.M, a.lda, s);
+    // bias gradient (A = dout^T): column sums of dout over the K rows (the thread workspace may be
+    // the slab just reduced: stream-ordered after the reduce)
+    if (a.dbias) colsum_bf16(a.dbias, (const bf16_t*)a.A, a.K, a.M, a.lda, s);
 }
 
 void gemm_bf16(const GemmArgs& a, hipStream_t s) {
@@ -1744,16 +1408,10 @@ void gemm_bf16(const GemmArgs& a, hipStream_t s) {
                   a.M, a.N, a.K, a.lda, a.ldb);
         return;
     }
-    if ((gemm_variant() == 4 || gemm_variant() == 5) && a.K % g4::KTILE == 0 && a.M >= 256 && a.N >= 128 &&
-        (a.epi != EPI_F32_ATOMIC || a.N % 4 == 0)) {
-        gemm_bf16_g4(a, s);
-        return;
-    }
     // split-K weight gradients (M/N-contiguous operands, K = the token count) run on the 256x128
     // two-per-CU engine: 3-9 % faster than 256x256 on every ViT-B/16 wgrad shape (r02,
     // tools/bench_gemm.py), the other GEMMs are faster on 256x256
-    if ((gemm_variant() == 2 || gemm_variant() == 7 || gemm_variant() == 9 || gemm_variant() == 10 || gemm_variant() == 11) &&
-        a.epi == EPI_F32_ATOMIC && !a.a_kcontig && !a.b_kcontig &&
+    if (gemm_variant() != 1 && a.epi == EPI_F32_ATOMIC && !a.a_kcontig && !a.b_kcontig &&
         a.K % g4::KTILE == 0 && a.M >= 256 && a.N >= 128 && a.N % 4 == 0 &&
         (a.splitk > 0 || !a.ws ||
          (size_t)choose_split_g4(cdiv(a.M, g4::BM) * cdiv(a.N, g4::BN), a.K / g4::KTILE) * a.M * a.N * sizeof(float) <=

@@ -20,7 +20,7 @@ struct GemmParams {
     int no_epi;  // diagnostic (gemm_bf16_set_debug): skip the epilogue, keep the accumulators live
     int dbg;     // diagnostic flags (gemm_bf16_set_debug & 0xF0): 16 = persistent engine drains its
                  // epilogue stores (vmcnt(0)) before the next tile's main loop
-    int stagger;  // two-per-CU engines: first-round delay (100 MHz ticks) of the CU's second workgroup
+    int stagger;  // two-per-CU engine: first-round delay (100 MHz ticks) of the CU's second workgroup
     unsigned long long* trace;  // diagnostic: [workgroup][4] start, main-loop end, end, hw id
     int tiles;   // output tiles of the launch (the grid is tiles x K-splits)
     int gm;      // persistent engine tile order: groups of gm row panels, column-major inside a group
@@ -32,11 +32,6 @@ struct GemmParams {
     uint8_t* mxc_s;
     long long mxc_ld;
     int mxc_off, mxc_rg;
-    // persistent engine with a split tail (variant 10): the last, partly filled round's tiles run as
-    // tsplit K-ranges of kchunk each into fp32 partial tiles tpart[tile][part][256][256]; tfull = the
-    // tiles of the full rounds (gemm_tail_fix_k finishes the tail tiles)
-    int tsplit, tfull;
-    float* tpart;
 };
 
 // E8M0 scale byte of an MX block: X + 127 with X = ceil(log2(amax / 448)) (no element overflows
@@ -123,7 +118,7 @@ __device__ __forceinline__ epi_u32x4 epi_ld16(const GemmParams&, const void* q) 
     return *reinterpret_cast<const epi_u32x4*>(q);
 }
 
-// Two workgroups per CU (g4 engines): workgroups b and b + 256 of a launch share a CU
+// Two workgroups per CU (the g4 engine): workgroups b and b + 256 of a launch share a CU
 // (tools/probe_placement.hip), and every tile takes the same time, so without help the two start,
 // reach their epilogues and finish together, round after round.  Delaying the second workgroup of
 // each CU in the first round by about half a tile keeps the pair half a tile apart for the whole

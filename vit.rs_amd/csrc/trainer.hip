@@ -292,10 +292,6 @@ struct Trainer {
     float* params = nullptr;
     float* grads = nullptr;
     float* gemm_ws = nullptr;     // split-K slabs of the wgrad GEMMs (stream-ordered on s)
-    // GEMM variant 10 (split tail round): fp32 partial tiles, one buffer per concurrent stream
-    // (ms[0..MAXMB-1], s2): 256 x 256 KiB at most per GEMM (gemm.hip launch_g2)
-    float* tail_buf[MAXMB + 1]{};
-    size_t tail_bytes = 0;
     float* attn_part = nullptr;   // per-(b,h) qkv-bias partial sums of the attention backward
     size_t gemm_ws_bytes = 0;
     bf16_t* pbf = nullptr;
@@ -563,19 +559,8 @@ struct Trainer {
         ev_used = 0;
     }
 
-    // the stream's own partial-tile buffer for GEMM variant 10 (never the shared thread workspace:
-    // the micro-batch streams run GEMMs concurrently)
-    void set_tail(GemmArgs& a, hipStream_t st) {
-        if (a.tail_ws || !tail_bytes) return;
-        int k = MAXMB;  // s2
-        for (int i = 0; i < MAXMB; i++)
-            if (st == ms[i]) k = i;
-        a.tail_ws = tail_buf[k];
-        a.tail_ws_bytes = tail_bytes;
-    }
     void gemm(int cls, GemmArgs a, bool bf, hipStream_t st = nullptr) {
         if (!st) st = s;
-        if (bf) set_tail(a, st);
         tbeg(cls, 2.0 * a.M * (double)a.N * a.K, st);
         if (bf) gemm_bf16(a, st); else gemm_f32(a, st);
         tend();
@@ -697,10 +682,6 @@ struct Trainer {
             gemm_ws_bytes = (size_t)32 << 20;
             gemm_ws = alloc<float>((long long)(gemm_ws_bytes / sizeof(float)));
         }
-        if (lowp() && gemm_variant_selected() == 10) {  // (A/B runs only: VIT_GEMM=10 at build time)
-            tail_bytes = (size_t)gemm_cu_count() * 256 * 256 * sizeof(float);
-            for (int k = 0; k <= MAXMB; k++) tail_buf[k] = alloc<float>((long long)(tail_bytes / sizeof(float)));
-        }
         if (lowp()) {
             if (!(attn_fused_supported(T, C, NH) || attn_generic_supported(T, C, NH)) || C % 8) {
                 set_error("trainer: bf16 / fp8 path needs head size 32, 64, 80, 96 or 128 and C %% 8 == 0 (T=%d C=%d NH=%d)", T, C, NH);
@@ -801,10 +782,10 @@ struct Trainer {
                     wg_b.q = alloc<uint8_t>(4LL * C * kp);
                     wg_b.s = alloc<uint8_t>((long long)mx_scale_bytes(4LL * C, (int)kp));
                     const char* lx = getenv("VIT_FP8_LN_MX");
-                ln_mx = !(lx && lx[0] == '0');
-                const char* lbx = getenv("VIT_FP8_LNB_MX");
-                lnb_mx = !(lbx && lbx[0] == '0');
-                const char* rc = getenv("VIT_FP8_ROWCOL");
+                    ln_mx = !(lx && lx[0] == '0');
+                    const char* lbx = getenv("VIT_FP8_LNB_MX");
+                    lnb_mx = !(lbx && lbx[0] == '0');
+                    const char* rc = getenv("VIT_FP8_ROWCOL");
                     rowcol_ok = !(rc && rc[0] == '0');
                     kp_tok = kp;
                     if (rowcol_ok) {
@@ -1119,13 +1100,11 @@ struct Trainer {
                 im2col_pad_bf16(patches_bf + img0 * NP * KPP, pixels + img0 * 3 * cfg.img * cfg.img, Bm, cfg.img,
                                 cfg.patch, KPP, st);
                 a.A = patches_bf + img0 * NP * KPP; a.lda = KPP; a.B = wpatch_pad; a.ldb = KPP; a.K = KPP;
-                set_tail(a, st);
                 gemm_bf16(a, st);
             } else {
                 im2col_bf16(patches_bf + img0 * NP * KP, pixels + img0 * 3 * cfg.img * cfg.img, Bm, cfg.img,
                             cfg.patch, st);
                 a.A = patches_bf + img0 * NP * KP; a.lda = KP; a.B = W(P_PATCH_W); a.ldb = KP;
-                set_tail(a, st);
                 gemm_bf16(a, st);
             }
             patch_assemble(encoded + img0 * T * C, emb_tmp + img0 * NP * C, P(P_CLS), P(P_WPE), Bm, NP, C, st);
