@@ -92,7 +92,8 @@ int vit_trainer_step(vit_trainer_t* t, float lr); /* waits for the all-reduce, t
 /* AdamW: the update the reference's m_memory / v_memory (train_vit.rs:73-74)
  * were allocated for, which its SGD optimizer_step (:737) never runs.  t = number of AdamW steps
  * so far + 1 (kept by the trainer, saved in checkpoints); m, v are allocated and zeroed on the
- * first call.  Decoupled weight decay on every parameter:
+ * first call.  Decoupled weight decay, on every parameter unless parameter groups (below) scale it
+ * per tensor (lr -> lr * lr_mul, wd -> weight_decay * wd_mul of the parameter's tensor and layer):
  *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g g;  p -= lr (m/(1-b1^t) / (sqrt(v/(1-b2^t)) + eps) + wd p) */
 int vit_trainer_step_adamw(vit_trainer_t* t, float lr, float beta1, float beta2, float eps,
                            float weight_decay);
@@ -116,6 +117,27 @@ int vit_trainer_set_grad_clip(vit_trainer_t* t, float max_norm);
 /* global L2 norm of the gradients the last clipped optimizer step used (after the all-reduce under
  * DP); -1 if no step has computed one.  Synchronous. */
 float vit_trainer_grad_norm(vit_trainer_t* t);
+/* ---- parameter groups: per-tensor, per-layer multipliers of the learning rate and of
+ *      the weight decay, applied inside the fused optimizer kernels of vit_trainer_step,
+ *      vit_trainer_step_adamw and vit_trainer_train_step (the early per-chunk SGD included).  For the
+ *      entry e of a parameter's tensor and layer the update runs with lr_e = lr * lr_mul[e] and
+ *      wd_e = weight_decay * wd_mul[e], each one fp32 multiply rounded on its own, in place of lr and
+ *      weight_decay; under clipping on g' = c * g as before.  1.0f * x == x, so all-ones multipliers
+ *      give the bits of the ungrouped step.  SGD has no weight decay and uses lr_mul only.
+ *      lr_mul == 0 freezes a tensor's values; AdamW's m and v of that tensor still advance (as in a
+ *      torch parameter group with lr = 0), and its gradient is still computed.
+ *      vit_trainer_grad_norm and the clip factor ignore the groups: the norm is over all raw gradients.
+ *      Under data parallelism every rank must set the same tables. ---- */
+/* lr_mul, wd_mul: [20 * num_layers] floats in the indexing of vit_layout_query's tensor_off
+ * (tensor ti of the canonical order, layer l at [ti * num_layers + l]; unlayered tensors use l = 0 and
+ * their other entries are ignored and read back as 1).  Either NULL = all ones.  Both NULL = groups
+ * off (the default).  Every used entry must be finite and >= 0; otherwise non-zero + vit_last_error
+ * and the previous setting stays.  A hyper-parameter: persists across steps, not written to
+ * checkpoints.  Call between steps; synchronous (waits for the steps in flight). */
+int vit_trainer_set_param_groups(vit_trainer_t* t, const float* lr_mul, const float* wd_mul);
+/* the multipliers in force (ones when off; either pointer may be NULL); *on (nullable) = 1 if
+ * groups are on */
+int vit_trainer_get_param_groups(vit_trainer_t* t, float* lr_mul, float* wd_mul, int* on);
 /* canonical host copies of m, v (either may be NULL) and the step count; synchronous */
 int vit_trainer_get_adamw_state(vit_trainer_t* t, float* m, float* v, int* step);
 /* eval: forward of the current batch, then top-1 per image on the device.

@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("VIT_LIB") or os.path.join(HERE, "libvit_hip.so")  # V
 
 from . import data  # noqa: E402  (configs, canonical layout, seeded synthetic inputs)
 from . import mix  # noqa: E402  (mixup / cutmix draws and their numpy statement)
+from . import groups  # noqa: E402  (parameter-group tables: no_decay, layer_decay)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
@@ -149,6 +150,8 @@ _SIGS = {
     "vit_trainer_step_adamw": (I, [P, F, F, F, F, F]),
     "vit_trainer_get_adamw_state": (I, [P, P, P, ctypes.POINTER(I)]),
     "vit_trainer_set_grad_clip": (I, [P, F]), "vit_trainer_grad_norm": (F, [P]),
+    "vit_trainer_set_param_groups": (I, [P, P, P]),
+    "vit_trainer_get_param_groups": (I, [P, P, P, ctypes.POINTER(I)]),
     "vit_trainer_eval": (I, [P, P, ctypes.POINTER(I)]),
     # checkpoints (include/vit_checkpoint.h; host-only)
     "vit_config_num_params": (LL, [ctypes.POINTER(VitConfigC)]),
@@ -653,6 +656,29 @@ class ViT:
         n = float(lib().vit_trainer_grad_norm(self.h))
         check("grad_norm")
         return n
+
+    def set_param_groups(self, lr_mul=None, wd_mul=None):
+        """Per-tensor, per-layer multipliers of lr and weight decay for every later optimizer step
+        (vit_trainer_set_param_groups).  Each is None (ones), an array [20, L] or a dict {tensor name
+        (data.PARAM_NAMES): scalar or length-L sequence}; see groups.no_decay / groups.layer_decay.
+        Both None switches groups off.  lr_mul 0 freezes a tensor (AdamW's m, v still advance)."""
+        ptrs, keep = [], []
+        for tab in (lr_mul, wd_mul):
+            if tab is None:
+                ptrs.append(None)
+            else:
+                a = groups.expand(self.cfg, tab)
+                keep.append(a)
+                ptrs.append(a.ctypes.data_as(P))
+        self._ok(lib().vit_trainer_set_param_groups(self.h, *ptrs), "set_param_groups")
+
+    def param_groups(self):
+        """(lr_mul [20, L], wd_mul [20, L], on): the multipliers in force (ones when off)."""
+        shape = (len(data.PARAM_NAMES), self.cfg.num_layers)
+        lr, wd, on = np.empty(shape, np.float32), np.empty(shape, np.float32), ctypes.c_int()
+        self._ok(lib().vit_trainer_get_param_groups(self.h, lr.ctypes.data_as(P), wd.ctypes.data_as(P),
+                                                    ctypes.byref(on)), "get_param_groups")
+        return lr, wd, bool(on.value)
 
     def adamw_state(self):
         """(m, v, t) in canonical order."""

@@ -191,6 +191,99 @@ __device__ __forceinline__ float adamw_update(float p, float g, float& m, float&
     return p - lr * (mh / (__builtin_sqrtf(vh) + eps) + wd * p);
 }
 
+// Parameter groups: per-(tensor, layer) multipliers of lr and weight decay inside
+// the fused optimizer kernels.  A segment is one placement of the arena layout with the alignment
+// padding behind it (starts are multiples of 64 elements); every segment is cut into tiles of
+// GROUP_TILE elements (the last one of a segment may be short), numbered in arena order.  A
+// workgroup takes whole tiles, finds the tile's segment once (a binary search over the prefix table
+// tile0 with wave-uniform values: scalar loads, no per-lane lookup) and runs the ungrouped float4
+// update over it with that segment's lr_e = lr * lr_mul and wd_e = wd * wd_mul.
+constexpr int GROUP_THREADS = 256;
+constexpr int GROUP_UNROLL = 4;                                  // float4s per thread and tile
+constexpr int GROUP_TILE4 = GROUP_THREADS * GROUP_UNROLL;         // float4s per tile
+constexpr int GROUP_TILE = GROUP_TILE4 * 4;                       // elements per tile
+struct GroupTab {
+    const int* tile0;        // [nseg + 1] first tile of segment s; tile0[nseg] = number of tiles
+    const long long* start;  // [nseg + 1] first element of segment s; start[nseg] = arena size
+    const float* lr_mul;     // [nseg]
+    const float* wd_mul;     // [nseg]
+    int nseg;
+};
+// lr_e / wd_e: one fp32 multiply rounded on its own (1.0f * x == x: all-ones groups change no bit)
+__device__ __forceinline__ float group_hp(float base, float mul) {
+#pragma clang fp contract(off)
+    return base * mul;
+}
+// the segment of `tile` (0 <= tile < tile0[nseg]; tile0 is strictly increasing), the tile's first
+// element and its length in float4s (1 .. GROUP_TILE4).  `tile` must be wave-uniform.
+__device__ __forceinline__ int group_tile(const GroupTab& gt, int tile, long long& beg, int& n4) {
+    int lo = 0, hi = gt.nseg;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (gt.tile0[mid] <= tile) lo = mid; else hi = mid;
+    }
+    beg = gt.start[lo] + (long long)(tile - gt.tile0[lo]) * GROUP_TILE;
+    const long long left = (gt.start[lo + 1] - beg) >> 2;
+    n4 = left < GROUP_TILE4 ? (int)left : GROUP_TILE4;
+    return lo;
+}
+// the float4 updates the ungrouped and the grouped kernels share
+template <bool CLIP>
+__device__ __forceinline__ void sgd_update4(float4& pv, float4 gv, float lr, float c) {
+    if (CLIP) {
+        gv.x = clip_scale(c, gv.x); gv.y = clip_scale(c, gv.y);
+        gv.z = clip_scale(c, gv.z); gv.w = clip_scale(c, gv.w);
+    }
+    pv.x = sgd_update(pv.x, gv.x, lr); pv.y = sgd_update(pv.y, gv.y, lr);
+    pv.z = sgd_update(pv.z, gv.z, lr); pv.w = sgd_update(pv.w, gv.w, lr);
+}
+template <bool CLIP>
+__device__ __forceinline__ void adamw_update4(float4& pv, float4 gv, float4& mv, float4& vv, float lr, float b1,
+                                              float b2, float omb1, float omb2, float bc1, float bc2, float eps,
+                                              float wd, float c) {
+    if (CLIP) {
+        gv.x = clip_scale(c, gv.x); gv.y = clip_scale(c, gv.y);
+        gv.z = clip_scale(c, gv.z); gv.w = clip_scale(c, gv.w);
+    }
+    pv.x = adamw_update(pv.x, gv.x, mv.x, vv.x, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
+    pv.y = adamw_update(pv.y, gv.y, mv.y, vv.y, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
+    pv.z = adamw_update(pv.z, gv.z, mv.z, vv.z, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
+    pv.w = adamw_update(pv.w, gv.w, mv.w, vv.w, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
+}
+// One tile of the grouped SGD: n4 float4s from element beg (a multiple of 64), hyper-parameters
+// uniform over the tile.  A full tile issues its GROUP_UNROLL loads per array before the first use.
+// SHADOW: also pbf = bf16(p), as the ungrouped bf16 kernel.
+template <bool CLIP, bool SHADOW>
+__device__ __forceinline__ void sgd_group_tile(float* __restrict__ p, bf16_t* __restrict__ pbf,
+                                               const float* __restrict__ g, long long beg, int n4, float lr,
+                                               float c) {
+    float4* __restrict__ p4 = reinterpret_cast<float4*>(p + beg);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + beg);
+    uint2* __restrict__ b2 = SHADOW ? reinterpret_cast<uint2*>(pbf + beg) : nullptr;
+    if (n4 == GROUP_TILE4) {
+        float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL];
+#pragma unroll
+        for (int k = 0; k < GROUP_UNROLL; k++) {
+            pv[k] = p4[threadIdx.x + k * GROUP_THREADS];
+            gv[k] = g4[threadIdx.x + k * GROUP_THREADS];
+        }
+#pragma unroll
+        for (int k = 0; k < GROUP_UNROLL; k++) {
+            const int i = threadIdx.x + k * GROUP_THREADS;
+            sgd_update4<CLIP>(pv[k], gv[k], lr, c);
+            p4[i] = pv[k];
+            if (SHADOW) b2[i] = make_uint2(pack_bf16x2(pv[k].x, pv[k].y), pack_bf16x2(pv[k].z, pv[k].w));
+        }
+    } else {
+        for (int i = threadIdx.x; i < n4; i += GROUP_THREADS) {
+            float4 pv = p4[i];
+            sgd_update4<CLIP>(pv, g4[i], lr, c);
+            p4[i] = pv;
+            if (SHADOW) b2[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
+        }
+    }
+}
+
 // XCD-aware bijective remap of a linear workgroup id (cdna_hip_programming.md §5, "XCD swizzle
 // must be bijective"): blocks dealt round-robin over 8 XCDs get contiguous tile ranges per XCD.
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {

@@ -60,6 +60,20 @@ __global__ void sgd_clip_k(float* __restrict__ p, const float* __restrict__ g, l
          i += (long long)gridDim.x * blockDim.x)
         p[i] = sgd_update(p[i], clip_scale(c, g[i]), lr);
 }
+// the fp32-mode update with parameter groups (common.h GroupTab): workgroups stride over the tiles
+// [tile_begin, tile_begin + ntiles) of the whole arena p / g, lr_e = lr * lr_mul[segment] per tile
+template <bool CLIP>
+__global__ __launch_bounds__(GROUP_THREADS) void sgd_groups_k(float* __restrict__ p, const float* __restrict__ g,
+                                                              GroupTab gt, int tile_begin, int ntiles, float lr,
+                                                              const ClipRec* __restrict__ rec) {
+    const float c = CLIP ? rec->c : 1.0f;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        long long beg;
+        int n4;
+        const int seg = group_tile(gt, tile_begin + t, beg, n4);
+        sgd_group_tile<CLIP, false>(p, nullptr, g, beg, n4, group_hp(lr, gt.lr_mul[seg]), c);
+    }
+}
 
 // ------------------------------------------------------------------ sum of squares (gradient norm)
 // slots[blockIdx.x] = sum of x[i]^2 over this workgroup's grid-stride share of x[0..n): every element
@@ -922,6 +936,16 @@ void sgd_clip(float* p, const float* g, long long n, float lr, const ClipRec* re
     if (n <= 0) return;
     sgd_clip_k<<<grid_for(n, 256), 256, 0, s>>>(p, g, n, lr, rec);
     after_launch("sgd_step_clipped");
+}
+int group_grid(int ntiles) { return ntiles < 2048 ? ntiles : 2048; }
+void sgd_groups(float* p, const float* g, const GroupTab& gt, int tile_begin, int ntiles, float lr,
+                const ClipRec* rec, hipStream_t s) {
+    if (ntiles <= 0) return;
+    if (rec)
+        sgd_groups_k<true><<<group_grid(ntiles), GROUP_THREADS, 0, s>>>(p, g, gt, tile_begin, ntiles, lr, rec);
+    else
+        sgd_groups_k<false><<<group_grid(ntiles), GROUP_THREADS, 0, s>>>(p, g, gt, tile_begin, ntiles, lr, nullptr);
+    after_launch(rec ? "sgd_step_groups_clipped" : "sgd_step_groups");
 }
 // a function of n alone (not of the device or of anything scheduling-dependent): one workgroup per
 // 4096 elements (four 16-byte loads per thread), at most 1024

@@ -11,6 +11,7 @@
 //   * optional per-kernel-class HIP-event timing on the compute stream.
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -85,12 +86,7 @@ __device__ __forceinline__ void sgd_bf16_body(float* __restrict__ p, bf16_t* __r
          i += (long long)gridDim.x * blockDim.x) {
         float4 pv = reinterpret_cast<float4*>(p)[i];
         float4 gv = reinterpret_cast<const float4*>(g)[i];
-        if (CLIP) {
-            gv.x = clip_scale(c, gv.x); gv.y = clip_scale(c, gv.y);
-            gv.z = clip_scale(c, gv.z); gv.w = clip_scale(c, gv.w);
-        }
-        pv.x = sgd_update(pv.x, gv.x, lr); pv.y = sgd_update(pv.y, gv.y, lr);
-        pv.z = sgd_update(pv.z, gv.z, lr); pv.w = sgd_update(pv.w, gv.w, lr);
+        sgd_update4<CLIP>(pv, gv, lr, c);
         reinterpret_cast<float4*>(p)[i] = pv;
         reinterpret_cast<uint2*>(pbf)[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
     }
@@ -125,14 +121,7 @@ __device__ __forceinline__ void adamw_body(float* __restrict__ p, bf16_t* __rest
         float4 gv = reinterpret_cast<const float4*>(g)[i];
         float4 mv = reinterpret_cast<float4*>(m)[i];
         float4 vv = reinterpret_cast<float4*>(v)[i];
-        if (CLIP) {
-            gv.x = clip_scale(c, gv.x); gv.y = clip_scale(c, gv.y);
-            gv.z = clip_scale(c, gv.z); gv.w = clip_scale(c, gv.w);
-        }
-        pv.x = adamw_update(pv.x, gv.x, mv.x, vv.x, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
-        pv.y = adamw_update(pv.y, gv.y, mv.y, vv.y, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
-        pv.z = adamw_update(pv.z, gv.z, mv.z, vv.z, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
-        pv.w = adamw_update(pv.w, gv.w, mv.w, vv.w, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
+        adamw_update4<CLIP>(pv, gv, mv, vv, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, c);
         reinterpret_cast<float4*>(p)[i] = pv;
         reinterpret_cast<float4*>(m)[i] = mv;
         reinterpret_cast<float4*>(v)[i] = vv;
@@ -156,6 +145,71 @@ __global__ void adamw_clip_k(float* __restrict__ p, bf16_t* __restrict__ pbf, co
                              float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd,
                              const ClipRec* __restrict__ rec) {
     adamw_body<true>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, rec->c);
+}
+// ---- parameter groups (common.h GroupTab): the same updates over the tiles
+// [tile_begin, tile_begin + ntiles) of the whole arena, lr_e = lr * lr_mul and wd_e = wd * wd_mul of
+// the tile's segment (uniform per workgroup iteration).  A gradient chunk is a tile sub-range.
+template <bool CLIP>
+__global__ __launch_bounds__(GROUP_THREADS) void sgd_bf16_groups_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
+                                                                   const float* __restrict__ g, GroupTab gt,
+                                                                   int tile_begin, int ntiles, float lr,
+                                                                   const ClipRec* __restrict__ rec) {
+    const float c = CLIP ? rec->c : 1.0f;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        long long beg;
+        int n4;
+        const int seg = group_tile(gt, tile_begin + t, beg, n4);
+        sgd_group_tile<CLIP, true>(p, pbf, g, beg, n4, group_hp(lr, gt.lr_mul[seg]), c);
+    }
+}
+template <bool CLIP>
+__global__ __launch_bounds__(GROUP_THREADS) void adamw_groups_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
+                                                                const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, GroupTab gt, int tile_begin,
+                                                                int ntiles, float lr, float b1, float b2, float omb1,
+                                                                float omb2, float bc1, float bc2, float eps, float wd,
+                                                                const ClipRec* __restrict__ rec) {
+    const float c = CLIP ? rec->c : 1.0f;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        long long beg;
+        int n4;
+        const int seg = group_tile(gt, tile_begin + t, beg, n4);
+        const float lr_e = group_hp(lr, gt.lr_mul[seg]), wd_e = group_hp(wd, gt.wd_mul[seg]);
+        float4* __restrict__ p4 = reinterpret_cast<float4*>(p + beg);
+        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + beg);
+        float4* __restrict__ m4 = reinterpret_cast<float4*>(m + beg);
+        float4* __restrict__ v4 = reinterpret_cast<float4*>(v + beg);
+        uint2* __restrict__ s2 = pbf ? reinterpret_cast<uint2*>(pbf + beg) : nullptr;
+        if (n4 == GROUP_TILE4) {  // a full tile: every load issued before the first use
+            float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL], mv[GROUP_UNROLL], vv[GROUP_UNROLL];
+#pragma unroll
+            for (int k = 0; k < GROUP_UNROLL; k++) {
+                const int i = threadIdx.x + k * GROUP_THREADS;
+                pv[k] = p4[i];
+                gv[k] = g4[i];
+                mv[k] = m4[i];
+                vv[k] = v4[i];
+            }
+#pragma unroll
+            for (int k = 0; k < GROUP_UNROLL; k++) {
+                const int i = threadIdx.x + k * GROUP_THREADS;
+                adamw_update4<CLIP>(pv[k], gv[k], mv[k], vv[k], lr_e, b1, b2, omb1, omb2, bc1, bc2, eps, wd_e, c);
+                p4[i] = pv[k];
+                m4[i] = mv[k];
+                v4[i] = vv[k];
+                if (s2) s2[i] = make_uint2(pack_bf16x2(pv[k].x, pv[k].y), pack_bf16x2(pv[k].z, pv[k].w));
+            }
+        } else {
+            for (int i = threadIdx.x; i < n4; i += GROUP_THREADS) {
+                float4 pv = p4[i], mv = m4[i], vv = v4[i];
+                adamw_update4<CLIP>(pv, g4[i], mv, vv, lr_e, b1, b2, omb1, omb2, bc1, bc2, eps, wd_e, c);
+                p4[i] = pv;
+                m4[i] = mv;
+                v4[i] = vv;
+                if (s2) s2[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
+            }
+        }
+    }
 }
 // top-1 of each logits row (first index among equal maxima, as numpy.argmax) and the count of
 // rows whose prediction equals the label (eval path).  One wave per row.
@@ -1544,6 +1598,13 @@ struct Trainer {
             VIT_HIP(hipEventRecord(e, ms[k]));
             VIT_HIP(hipStreamWaitEvent(s_comm, e, 0));
         }
+        if (groups_on) {  // the whole-arena grouped kernel over the chunk's tiles: the same bits
+            const int t0 = grp_chunk_tile[c], nt = grp_chunk_tile[c + 1] - t0;
+            sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s_comm>>>(params, pbf, grads, grp_tab, t0, nt,
+                                                                                   early_lr, nullptr);
+            after_launch("sgd_bf16_groups_chunk");
+            return;
+        }
         const long long o = chunk_off[c], n = chunk_off[c + 1] - chunk_off[c];
         sgd_bf16_k<<<grid_for(n / 4, 256), 256, 0, s_comm>>>(params + o, pbf + o, grads + o, n, early_lr);
         after_launch("sgd_bf16_chunk");
@@ -1719,6 +1780,94 @@ struct Trainer {
         VIT_HIP(hipMemsetAsync(adam_v, 0, arena_elems * 4, s));
         return true;
     }
+    // Parameter groups (vit_trainer_set_param_groups): per-(tensor, layer) multipliers
+    // of lr and weight decay.  grp_lr / grp_wd keep the setting in the canonical [20 * L] indexing
+    // (ignored entries as 1); the device tables are per segment in arena order (common.h GroupTab).
+    // Chunk boundaries are segment boundaries, so chunk c is the tile range
+    // [grp_chunk_tile[c], grp_chunk_tile[c + 1]) of the same kernel (early SGD).
+    bool groups_on = false;
+    std::vector<float> grp_lr, grp_wd;
+    std::vector<int> grp_seg_entry;  // segment s (arena order) -> canonical entry ti * L + l
+    int grp_chunk_tile[VIT_MAX_LAYERS + 3]{};
+    GroupTab grp_tab{};
+    float *grp_dev_lr = nullptr, *grp_dev_wd = nullptr;
+    bool group_used(int ti, int l) const { return layered(ti) ? true : l == 0; }
+    // segments and tiles of the layout; the static device tables.  Once, on the first enabling.
+    bool groups_enable() {
+        if (grp_tab.tile0) return true;
+        for (int ti = 0; ti < 20; ti++)
+            for (int l = 0; l < L; l++)
+                if (group_used(ti, l)) grp_seg_entry.push_back(ti * L + l);
+        std::sort(grp_seg_entry.begin(), grp_seg_entry.end(), [&](int a, int b) { return off[a] < off[b]; });
+        const int nseg = (int)grp_seg_entry.size();  // 12 L + 8
+        std::vector<long long> start(nseg + 1);
+        std::vector<int> tile0(nseg + 1);
+        for (int sgi = 0; sgi < nseg; sgi++) start[sgi] = off[grp_seg_entry[sgi]];
+        start[nseg] = arena_elems;
+        tile0[0] = 0;
+        for (int sgi = 0; sgi < nseg; sgi++)
+            tile0[sgi + 1] = tile0[sgi] + (int)((start[sgi + 1] - start[sgi] + GROUP_TILE - 1) / GROUP_TILE);
+        for (int c = 0, sgi = 0; c <= n_chunks; c++) {
+            while (sgi < nseg && start[sgi] < chunk_off[c]) sgi++;
+            if (start[sgi] != chunk_off[c]) {
+                set_error("parameter groups: chunk %d does not start a segment", c);
+                return false;
+            }
+            grp_chunk_tile[c] = tile0[sgi];
+        }
+        int* d_tile0 = alloc<int>(nseg + 1);
+        long long* d_start = alloc<long long>(nseg + 1);
+        grp_dev_lr = alloc<float>(nseg);
+        grp_dev_wd = alloc<float>(nseg);
+        if (!d_tile0 || !d_start || !grp_dev_lr || !grp_dev_wd) return false;
+        VIT_HIP(hipMemcpyAsync(d_tile0, tile0.data(), (size_t)(nseg + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        VIT_HIP(hipMemcpyAsync(d_start, start.data(), (size_t)(nseg + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+        VIT_HIP(hipStreamSynchronize(s));
+        if (has_error()) return false;
+        grp_tab = GroupTab{d_tile0, d_start, grp_dev_lr, grp_dev_wd, nseg};
+        return true;
+    }
+    // lr_mul / wd_mul canonical [20 * L], either NULL = ones, both NULL = off
+    bool set_groups(const float* lr_mul, const float* wd_mul) {
+        const int n = 20 * L;
+        if (!lr_mul && !wd_mul) {
+            groups_on = false;
+            grp_lr.assign(n, 1.0f);
+            grp_wd.assign(n, 1.0f);
+            return true;
+        }
+        std::vector<float> nl(n, 1.0f), nw(n, 1.0f);
+        for (int ti = 0; ti < 20; ti++)
+            for (int l = 0; l < L; l++) {
+                if (!group_used(ti, l)) continue;
+                const int e = ti * L + l;
+                const float a = lr_mul ? lr_mul[e] : 1.0f, b = wd_mul ? wd_mul[e] : 1.0f;
+                if (!(std::isfinite(a) && a >= 0.f && std::isfinite(b) && b >= 0.f)) {
+                    set_error("vit_trainer_set_param_groups: tensor %d layer %d: lr_mul %g / wd_mul %g is not "
+                              "finite and >= 0", ti, l, (double)a, (double)b);
+                    return false;
+                }
+                nl[e] = a;
+                nw[e] = b;
+            }
+        if (!groups_enable()) return false;
+        const int nseg = grp_tab.nseg;
+        std::vector<float> sl(nseg), sw(nseg);
+        for (int sgi = 0; sgi < nseg; sgi++) {
+            sl[sgi] = nl[grp_seg_entry[sgi]];
+            sw[sgi] = nw[grp_seg_entry[sgi]];
+        }
+        // on the trainer's stream, behind every step in flight (a step leaves s behind the side
+        // streams' optimizer work); synchronous, so the host vectors may go
+        VIT_HIP(hipMemcpyAsync(grp_dev_lr, sl.data(), (size_t)nseg * 4, hipMemcpyHostToDevice, s));
+        VIT_HIP(hipMemcpyAsync(grp_dev_wd, sw.data(), (size_t)nseg * 4, hipMemcpyHostToDevice, s));
+        VIT_HIP(hipStreamSynchronize(s));
+        if (has_error()) return false;
+        grp_lr.swap(nl);
+        grp_wd.swap(nw);
+        groups_on = true;
+        return true;
+    }
     // AdamW update t = adam_t + 1 (llm.c's update, which the reference's m/v buffers —
     // train_vit.rs:73-74 — were allocated for; its optimizer_step :737 is SGD)
     void step_adamw(float lr, const vit_adamw_t& hp) {
@@ -1731,7 +1880,22 @@ struct Trainer {
         const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)adam_t);
         const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)adam_t);
         tbeg(TC_SGD, 0);
-        if (clip_on()) {
+        if (groups_on) {  // one launch over every tile of the arena
+            const int nt = grp_chunk_tile[n_chunks];
+            bf16_t* shadow = lowp() ? pbf : nullptr;
+            if (clip_on()) {
+                clip_norm();
+                adamw_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
+                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, 1.0f - hp.beta1,
+                    1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay, clip_rec);
+                after_launch("adamw_groups_clipped");
+            } else {
+                adamw_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
+                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, 1.0f - hp.beta1,
+                    1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay, nullptr);
+                after_launch("adamw_groups");
+            }
+        } else if (clip_on()) {
             clip_norm();
             adamw_clip_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(
                 params, lowp() ? pbf : nullptr, grads, adam_m, adam_v, arena_elems, lr, hp.beta1, hp.beta2,
@@ -1758,7 +1922,24 @@ struct Trainer {
         }
         finish_allreduce();
         tbeg(TC_SGD, 0);
-        if (clip_on()) {
+        if (groups_on) {  // one launch over every tile of the arena
+            const int nt = grp_chunk_tile[n_chunks];
+            const ClipRec* rec = nullptr;
+            if (clip_on()) {
+                clip_norm();
+                rec = clip_rec;
+            }
+            if (!lowp()) {
+                sgd_groups(params, grads, grp_tab, 0, nt, lr, rec, s);
+            } else if (rec) {
+                sgd_bf16_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt, lr, rec);
+                after_launch("sgd_bf16_groups_clipped");
+            } else {
+                sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt, lr,
+                                                                                  nullptr);
+                after_launch("sgd_bf16_groups");
+            }
+        } else if (clip_on()) {
             clip_norm();
             if (lowp()) {
                 sgd_bf16_clip_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(params, pbf, grads, arena_elems, lr,
@@ -2032,6 +2213,27 @@ float vit_trainer_grad_norm(vit_trainer_t* h) {
     VIT_HIP(hipMemcpyAsync(&r, t.clip_rec, sizeof(r), hipMemcpyDeviceToHost, t.s));
     VIT_HIP(hipStreamSynchronize(t.s));
     return r.norm;
+}
+int vit_trainer_set_param_groups(vit_trainer_t* h, const float* lr_mul, const float* wd_mul) {
+    if (!h) {
+        set_error("vit_trainer_set_param_groups: null trainer");
+        return 1;
+    }
+    return h->t.set_groups(lr_mul, wd_mul) ? 0 : 1;
+}
+int vit_trainer_get_param_groups(vit_trainer_t* h, float* lr_mul, float* wd_mul, int* on) {
+    if (!h) {
+        set_error("vit_trainer_get_param_groups: null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    const size_t n = (size_t)20 * t.L;
+    for (size_t e = 0; e < n; e++) {
+        if (lr_mul) lr_mul[e] = t.grp_lr.empty() ? 1.0f : t.grp_lr[e];
+        if (wd_mul) wd_mul[e] = t.grp_wd.empty() ? 1.0f : t.grp_wd[e];
+    }
+    if (on) *on = t.groups_on ? 1 : 0;
+    return 0;
 }
 int vit_trainer_get_adamw_state(vit_trainer_t* h, float* m, float* v, int* step) {
     auto& t = h->t;
