@@ -196,6 +196,10 @@ int vit_trainer_set_concurrency(vit_trainer_t* t, int on);
  *      gradient clipping on, bf16 / fp8 and concurrency on, 1 takes each gradient chunk's partial
  *      sums of squares on the side (all-reduce) stream as soon as the backward has finished the
  *      chunk, 0 takes them all at step time on the main stream (same bits either way),
+ *      "last_cls" = 1 (default; bf16 mode only, ignored in fp32 and fp8 mode): the classifier head reads
+ *      only the CLS row of each image, so the last block's attention projection, LayerNorm 2, fc + GELU
+ *      and fcproj and the fc / attention-projection input gradients run on the B CLS rows instead of all
+ *      B*T (same loss, logits and gradients bit for bit).  0: every row,
  *      "dp_probe" = 1: every gradient chunk is also copied, on the all-reduce stream right after
  *      its all-reduce, into a snapshot arena (read with vit_trainer_get_dp_snapshot) — a check
  *      that each overlapped chunk was final when it was reduced.

@@ -61,6 +61,14 @@ struct GemmArgs {
     // (0 = the engine's default, 45: a weight gradient beside other streams; the trainer passes 80 when
     // the kernel has the GPU to itself)
     int fill_pct = 0;
+    // gemm_bf16, row-gathered calls (the trainer's last block): the M rows are a strided
+    // selection (lda / ldc / ldaux = a multiple of the dense pitch) of a tensor whose other GEMMs run on
+    // the persistent 256x256 engine, so the call keeps that engine for any M >= 1 (one ragged row panel:
+    // the same tile code and K order as the full-size call, bit-identical rows) instead of dropping to
+    // the 128x128 kernel below M = 256.  Only where the shape is otherwise eligible (N >= 256,
+    // K % 64 == 0, K-contiguous A, no split-K; the persistent form for a K-contiguous B within the
+    // 2^31-byte operand spans, else the one-tile form); every other call dispatches as without it.
+    bool rows_gathered = false;
     // split-K workspace for EPI_F32_ATOMIC on the 256x256 kernel: partials go to fp32 slabs and
     // one reduce kernel adds them into C (no atomics).  nullptr = the calling thread's workspace
     // (ordered on the context stream); the trainer passes its own buffer for its stream.

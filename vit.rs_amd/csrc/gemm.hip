@@ -1419,7 +1419,12 @@ void gemm_bf16(const GemmArgs& a, hipStream_t s) {
         gemm_bf16_g4(a, s);
         return;
     }
-    const bool big = a.K % g2::KTILE == 0 && a.M >= 256 && a.N >= 256 && gemm_variant() != 1;
+    // a row-gathered call (GemmArgs::rows_gathered) below M = 256 stays on the 256x256 LDS-DMA engines
+    // as one ragged row panel (source rows clamped to M - 1, the epilogue masks m >= M): the persistent
+    // form where launch_g2 picks it, else the one-tile form, which computes the same bits.  K-contiguous
+    // A only (the M-contiguous stage clamps to M - 8) and no split-K
+    const bool gathered = a.rows_gathered && a.M >= 1 && a.a_kcontig && a.epi != EPI_F32_ATOMIC;
+    const bool big = a.K % g2::KTILE == 0 && (a.M >= 256 || gathered) && a.N >= 256 && gemm_variant() != 1;
     if (big) {
         const int tiles = cdiv(a.M, g2::BM) * cdiv(a.N, g2::BN);
         int split = 1;

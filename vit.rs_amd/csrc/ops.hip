@@ -171,10 +171,11 @@ __global__ __launch_bounds__(256) void ln_fwd_k(TO* __restrict__ out, float* __r
                                                 float* __restrict__ rstd,
                                                 const float* __restrict__ inp,
                                                 const float* __restrict__ w,
-                                                const float* __restrict__ b, long long rows, int C) {
+                                                const float* __restrict__ b, long long rows, int C,
+                                                long long rstride) {
     const int lane = threadIdx.x & 63;
-    const long long row = blockIdx.x * 4LL + (threadIdx.x >> 6);
-    if (row >= rows) return;
+    if (blockIdx.x * 4LL + (threadIdx.x >> 6) >= rows) return;
+    const long long row = (blockIdx.x * 4LL + (threadIdx.x >> 6)) * rstride;  // (the row in memory)
     const float* x = inp + row * C;
     float s = 0.f;
     for (int i = lane; i < C; i += 64) s += x[i];
@@ -288,10 +289,10 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_k(TO* __restrict__ out, float*
                                                     const float* __restrict__ inp,
                                                     const float* __restrict__ w,
                                                     const float* __restrict__ b, long long rows,
-                                                    int C) {
+                                                    int C, long long rstride) {
     const int lane = threadIdx.x & 63;
-    const long long row = blockIdx.x * 4LL + (threadIdx.x >> 6);
-    if (row >= rows) return;
+    if (blockIdx.x * 4LL + (threadIdx.x >> 6) >= rows) return;
+    const long long row = (blockIdx.x * 4LL + (threadIdx.x >> 6)) * rstride;  // (the row in memory)
     const float4* x4 = reinterpret_cast<const float4*>(inp + row * C);
     float4 v[NV];
 #pragma unroll
@@ -789,19 +790,19 @@ __global__ void patch_small_grads_fin_k(float* __restrict__ dcls, float* __restr
 // ------------------------------------------------------------------ launch helpers (internal)
 template <typename TO>
 static void ln_forward_any(TO* out, float* mean, float* rstd, const float* inp, const float* w,
-                           const float* b, long long rows, int C, hipStream_t s) {
+                           const float* b, long long rows, int C, hipStream_t s, long long rstride = 1) {
     if (rows <= 0) return;
     const int g = cdiv(rows, 4);
     const bool vec = C % 256 == 0 && C <= 2048 && (((uintptr_t)inp | (uintptr_t)out | (uintptr_t)w | (uintptr_t)b) & 15) == 0;
     switch (vec ? C / 256 : 0) {
-        case 1: ln_fwd_vec_k<1, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
-        case 2: ln_fwd_vec_k<2, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
-        case 3: ln_fwd_vec_k<3, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
-        case 4: ln_fwd_vec_k<4, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
-        case 5: ln_fwd_vec_k<5, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
-        case 6: ln_fwd_vec_k<6, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
-        case 8: ln_fwd_vec_k<8, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
-        default: ln_fwd_k<TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C); break;
+        case 1: ln_fwd_vec_k<1, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
+        case 2: ln_fwd_vec_k<2, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
+        case 3: ln_fwd_vec_k<3, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
+        case 4: ln_fwd_vec_k<4, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
+        case 5: ln_fwd_vec_k<5, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
+        case 6: ln_fwd_vec_k<6, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
+        case 8: ln_fwd_vec_k<8, TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
+        default: ln_fwd_k<TO><<<g, 256, 0, s>>>(out, mean, rstd, inp, w, b, rows, C, rstride); break;
     }
     after_launch("layernorm_forward");
 }
@@ -810,8 +811,8 @@ void ln_forward_f32(float* out, float* mean, float* rstd, const float* inp, cons
     ln_forward_any<float>(out, mean, rstd, inp, w, b, rows, C, s);
 }
 void ln_forward_bf16(bf16_t* out, float* mean, float* rstd, const float* inp, const float* w,
-                     const float* b, long long rows, int C, hipStream_t s) {
-    ln_forward_any<bf16_t>(out, mean, rstd, inp, w, b, rows, C, s);
+                     const float* b, long long rows, int C, hipStream_t s, long long row_stride) {
+    ln_forward_any<bf16_t>(out, mean, rstd, inp, w, b, rows, C, s, row_stride);
 }
 int ln_bwd_blocks(long long rows);
 template <typename TD, bool ST>

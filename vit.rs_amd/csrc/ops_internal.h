@@ -8,8 +8,10 @@ namespace vit {
 int grid_for(long long n, int threads);
 void ln_forward_f32(float* out, float* mean, float* rstd, const float* inp, const float* w,
                     const float* b, long long rows, int C, hipStream_t s);
+// row_stride: logical row r is row r * row_stride of out / inp / mean / rstd (the trainer's last block
+// normalises only the CLS row of each image, in place: stride T)
 void ln_forward_bf16(bf16_t* out, float* mean, float* rstd, const float* inp, const float* w,
-                     const float* b, long long rows, int C, hipStream_t s);
+                     const float* b, long long rows, int C, hipStream_t s, long long row_stride = 1);
 // dinp += LN_dinp(dout); dw / db += the column sums, in a fixed order through per-block partial
 // rows in ws (nullptr = thread workspace; ln_bwd_blocks(rows) * 2C floats)
 void ln_backward_f32(float* dinp, float* dw, float* db, const float* dout, const float* inp,

@@ -322,7 +322,7 @@ struct Trainer {
     // attention kernels of the main stream (they only read activations and write grads)
     hipStream_t s2 = nullptr;
     bool two_streams = true;
-    enum BwdEv { EV_RESA, EV_RESB, EV_DFCH, EV_DQKV, EV_W1, EV_W2, EV_W3, EV_W4, EV_JOIN, EV_SG, EV_PRE_IN, EV_PRE, EV_COUNT };
+    enum BwdEv { EV_RESA, EV_RESB, EV_DFCH, EV_DQKV, EV_W1, EV_W2, EV_W3, EV_W4, EV_JOIN, EV_SG, EV_PRE_IN, EV_PRE, EV_LC_IN, EV_LC, EV_COUNT };
     hipEvent_t bev[EV_COUNT]{};
     // micro-batches: the batch is processed as NMB row ranges on NMB streams (ms[0] = s), so the
     // kernels of one half (GEMM epilogue bursts, LayerNorm, attention) overlap the other's GEMM
@@ -777,6 +777,21 @@ struct Trainer {
                 a.fchg = alloc<bf16_t>(BT * 4 * C);
                 a.res3 = alloc<float>(BT * C);
             }
+            if (prec == VIT_BF16 && !has_error()) {
+                // last_cls: with the option on, the last block's forward writes only the CLS
+                // rows of these, while its full-size weight gradients, fcproj dgrad epilogue and LayerNorm 2
+                // backward still read every row of them against gradient rows that are exact zeros.  Cleared
+                // once here, so those products are 0 x finite (zeros, or rows an earlier last_cls=0 step
+                // left), never 0 x NaN from uninitialised memory: this is what makes the full-size weight
+                // gradients safe.
+                LayerActs& a = la[L - 1];
+                VIT_HIP(hipMemsetAsync(a.ln2_mean, 0, (size_t)BT * 4, s));
+                VIT_HIP(hipMemsetAsync(a.ln2_rstd, 0, (size_t)BT * 4, s));
+                VIT_HIP(hipMemsetAsync(a.res2, 0, (size_t)BT * C * 4, s));
+                VIT_HIP(hipMemsetAsync(a.ln2, 0, (size_t)BT * C * 2, s));
+                VIT_HIP(hipMemsetAsync(a.fchd, 0, (size_t)BT * 4 * C * 2, s));
+                VIT_HIP(hipMemsetAsync(a.fchg, 0, (size_t)BT * 4 * C * 2, s));
+            }
             dln_bf = alloc<bf16_t>(BT * C);
             dres_bf = alloc<bf16_t>(BT * C);
             dres_bf2 = alloc<bf16_t>(BT * C);
@@ -1050,6 +1065,49 @@ struct Trainer {
         tend();
     }
 
+    // ------------------------------------------------------------------ last_cls
+    // The head reads only the CLS row of each image from the last block's output, so in the last block
+    // the row-wise ops after attention (attention projection, LayerNorm 2, fc + GELU, fcproj, and the fc /
+    // attention-projection input gradients) run on the B CLS rows only, in place at row stride T in the
+    // buffers of the full-size step.  bf16 mode only (fp32 is the parity path; the fp8 column forms span
+    // 32-token blocks).  The last block's three weight gradients stay full size, and so do the two
+    // kernels that take its small gradients' partial sums (the fcproj dgrad: fc_b; LayerNorm 2 backward:
+    // ln2_w, ln2_b, attproj_b), so every gradient keeps the full-size step's bits; the gradient rows the
+    // trimmed kernels no longer write are cleared once per step (last_cls_clear).
+    bool last_cls = true;    // option last_cls
+    bool lc_active = false;  // the running step's forward ran trimmed (the backward follows it)
+    bool lc_dirty = true;    // a backward (or nothing yet) wrote the shared gradient scratch since the last clear
+    bool lc_pending = false; // the clears are in flight on s2 (EV_LC)
+    bool last_cls_on() const { return last_cls && prec == VIT_BF16; }
+    // dln_bf (the fc dgrad's output) and datty are scratch shared by all layers: after a backward they
+    // hold layer 0's rows.  The last block's LayerNorm 2 backward and attention backward read every row
+    // of them, and the trimmed fc / attproj dgrads write only the CLS rows, so the rest must be zero
+    // (what the full-size kernels computed there).  Once per step, on s2
+    // beside the forward: ordered by EV_LC_IN after everything enqueued on s so far (the previous
+    // backward's micro-batch streams and s2 have joined s), and the backward's first kernel waits for
+    // EV_LC (last_cls_wait) before any stream of it can write these buffers.
+    void last_cls_clear() {
+        if (!lc_dirty) return;
+        hipStream_t cs = s;
+        if (two_streams && s2) {
+            VIT_HIP(hipEventRecord(bev[EV_LC_IN], s));
+            VIT_HIP(hipStreamWaitEvent(s2, bev[EV_LC_IN], 0));
+            cs = s2;
+        }
+        VIT_HIP(hipMemsetAsync(dln_bf, 0, (size_t)BT * C * 2, cs));
+        VIT_HIP(hipMemsetAsync(datty, 0, (size_t)BT * C * 2, cs));
+        if (cs != s) {
+            VIT_HIP(hipEventRecord(bev[EV_LC], cs));
+            lc_pending = true;
+        }
+        lc_dirty = false;
+    }
+    void last_cls_wait() {
+        if (!lc_pending) return;
+        VIT_HIP(hipStreamWaitEvent(s, bev[EV_LC], 0));
+        lc_pending = false;
+    }
+
     // ------------------------------------------------------------------ head (both modes)
     // split-K of the M = B head GEMMs (bf16 / fp8 modes): about four 16-deep K-steps per work item.
     // The engine's rule stops at >= 8 K-steps per split (192-256 workgroups of 12-16 dependent
@@ -1136,6 +1194,8 @@ struct Trainer {
     void forward_bf16() {
         const int Bm = B / nmb;
         const long long R = (long long)Bm * T;  // rows per micro-batch
+        lc_active = last_cls_on();
+        if (lc_active) last_cls_clear();
         mb_fork();
         for (int mb = 0; mb < nmb; mb++) {
             // patch embedding (encoder_forward, train_vit.rs:196 -> ViT)
@@ -1167,6 +1227,13 @@ struct Trainer {
         for (int l = 0; l < L; l++) {
             LayerActs& a = la[l];
             const float* xl = l == 0 ? encoded : la[l - 1].res3;
+            // last_cls: the row-wise ops after attention take the Bm CLS rows (row stride T, in place)
+            const bool lc = lc_active && l == L - 1;
+            const int Mr = lc ? Bm : (int)R;
+            const long long rs = lc ? T : 1;
+            // ... on the engine their full-size form takes (GemmArgs::rows_gathered: R rows would run on the
+            // 256x256 engine, so do the Bm), which keeps every CLS row's bits what they were
+            const bool lcg = lc && R >= 256;
             for (int mb = 0; mb < nmb; mb++) {
                 hipStream_t st = ms[mb];
                 const long long r0 = (long long)mb * R;
@@ -1191,9 +1258,9 @@ struct Trainer {
                 attn_forward_fused(a.atty + r0 * C, a.lse + (long long)mb * Bm * NH * T, a.qkv + r0 * 3 * C, Bm, T, C, NH, st);
                 tend();
                 GemmArgs pr;
-                pr.A = a.atty + r0 * C; pr.lda = C; pr.B = W(P_ATTPROJW, l); pr.ldb = C; pr.C = a.res2 + r0 * C;
-                pr.ldc = C; pr.bias = P(P_ATTPROJB, l); pr.aux = x; pr.ldaux = C;
-                pr.M = (int)R; pr.N = C; pr.K = C; pr.epi = EPI_F32_RESID;
+                pr.A = a.atty + r0 * C; pr.lda = rs * C; pr.B = W(P_ATTPROJW, l); pr.ldb = C; pr.C = a.res2 + r0 * C;
+                pr.ldc = rs * C; pr.bias = P(P_ATTPROJB, l); pr.aux = x; pr.ldaux = rs * C;
+                pr.M = Mr; pr.N = C; pr.K = C; pr.epi = EPI_F32_RESID; pr.rows_gathered = lcg;
                 gemm_w(TC_PROJ_FWD, pr, P_ATTPROJW, l, false, mb, st, PRE_NONE, false, rc ? &c_atty : nullptr);
                 tbeg(TC_LN_FWD, 0, st);
                 if (lm)
@@ -1202,13 +1269,13 @@ struct Trainer {
                                   ln_left ? lnb_scr[mb] : nullptr);
                 else
                     ln_forward_bf16(a.ln2 + r0 * C, a.ln2_mean + r0, a.ln2_rstd + r0, a.res2 + r0 * C, P(P_LN2W, l),
-                                    P(P_LN2B, l), R, C, st);
+                                    P(P_LN2B, l), Mr, C, st, rs);
                 tend();
                 GemmArgs f;
                 // fc: fchg = gelu(pre) for fcproj, fchd = gelu'(pre) for the fcproj dgrad (one sigmoid)
-                f.A = a.ln2 + r0 * C; f.lda = C; f.B = W(P_FCW, l); f.ldb = C; f.C = a.fchd + r0 * 4 * C;
-                f.C2 = a.fchg + r0 * 4 * C; f.ldc = 4 * C; f.bias = P(P_FCB, l); f.M = (int)R; f.N = 4 * C;
-                f.K = C; f.epi = EPI_BF16_GELU_D;
+                f.A = a.ln2 + r0 * C; f.lda = rs * C; f.B = W(P_FCW, l); f.ldb = C; f.C = a.fchd + r0 * 4 * C;
+                f.C2 = a.fchg + r0 * 4 * C; f.ldc = rs * 4 * C; f.bias = P(P_FCB, l); f.M = Mr; f.N = 4 * C;
+                f.K = C; f.epi = EPI_BF16_GELU_D; f.rows_gathered = lcg;
                 if (epicol_on()) {  // the GELU output only as its row (mx_out) and column MX forms
                     const QMat g = fchgc_of(l);
                     f.C2 = nullptr;
@@ -1217,9 +1284,9 @@ struct Trainer {
                 gemm_w(TC_FC_FWD, f, P_FCW, l, false, mb, st, lm ? PRE_LN : PRE_NONE, fuse_mx,
                        rc && !lm ? &c_ln2 : nullptr);
                 GemmArgs fp;
-                fp.A = a.fchg + r0 * 4 * C; fp.lda = 4 * C; fp.B = W(P_FCPROJW, l); fp.ldb = 4 * C;
-                fp.C = a.res3 + r0 * C; fp.ldc = C; fp.bias = P(P_FCPROJB, l); fp.aux = a.res2 + r0 * C;
-                fp.ldaux = C; fp.M = (int)R; fp.N = C; fp.K = 4 * C; fp.epi = EPI_F32_RESID;
+                fp.A = a.fchg + r0 * 4 * C; fp.lda = rs * 4 * C; fp.B = W(P_FCPROJW, l); fp.ldb = 4 * C;
+                fp.C = a.res3 + r0 * C; fp.ldc = rs * C; fp.bias = P(P_FCPROJB, l); fp.aux = a.res2 + r0 * C;
+                fp.ldaux = rs * C; fp.M = Mr; fp.N = C; fp.K = 4 * C; fp.epi = EPI_F32_RESID; fp.rows_gathered = lcg;
                 gemm_w(TC_FCPROJ_FWD, fp, P_FCPROJW, l, false, mb, st, fuse_mx ? PRE_EPI : PRE_NONE);
             }
         }
@@ -1309,6 +1376,8 @@ struct Trainer {
 
     void backward_bf16() {
         pre_side_wait();  // the arena clear and the transposed weights (side pre-work on s2)
+        last_cls_wait();  // the per-step clears of dln_bf / datty (the micro-batch streams fork off s below)
+        lc_dirty = true;
         // the residual-gradient stream is "bf16 + lo8" (common.h: a bf16 plane, the GEMM operand,
         // plus a byte plane of its rounding residual; a 16-bit significand in 3 bytes): dres3 (the
         // layer output's gradient) in rbA/loA, dres2 in rbB/loB; each LayerNorm backward reads one
@@ -1331,6 +1400,15 @@ struct Trainer {
         for (int l = L - 1; l >= 0; l--) {
             LayerActs& a = la[l];
             const float* xl = l == 0 ? encoded : la[l - 1].res3;
+            // last_cls: dres3 is zero off the CLS rows (head_backward), so dfch, dln2 and dres2 are too: the
+            // fc and attproj input gradients run on the Bm CLS rows (row stride T, in place), and the rows
+            // they skip were cleared (last_cls_clear).  The weight gradients stay full size, and so do the
+            // fcproj dgrad and LayerNorm 2 backward, whose partial rows make fc_b, ln2_w, ln2_b and
+            // attproj_b: summed over the same rows in the same order, they keep their bits
+            const bool lc = lc_active && l == L - 1;
+            const int Mr = lc ? Bm : (int)R;
+            const long long rs = lc ? T : 1;
+            const bool lcg = lc && R >= 256;  // (as in forward_bf16: the engine of the full-size form)
             // rowcol: the weight gradients whose dout column form the dgrads' quantize step writes
             // are issued after those dgrads (s2 waits on the event recorded after the quantize)
             const bool rc = rowcol_on();
@@ -1367,8 +1445,9 @@ struct Trainer {
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d2;
-                d2.A = dfch + r0 * 4 * C; d2.lda = 4 * C; dgrad_b(d2, P_FCW, l, 4 * C, C);
-                d2.C = dln_bf + r0 * C; d2.ldc = C; d2.M = (int)R; d2.N = C; d2.K = 4 * C; d2.epi = EPI_BF16_STORE;
+                d2.A = dfch + r0 * 4 * C; d2.lda = rs * 4 * C; dgrad_b(d2, P_FCW, l, 4 * C, C);
+                d2.C = dln_bf + r0 * C; d2.ldc = rs * C; d2.M = Mr; d2.N = C; d2.K = 4 * C; d2.epi = EPI_BF16_STORE;
+                d2.rows_gathered = lcg;
                 gemm_w(TC_FC_DGRAD, d2, P_FCW, l, true, mb, ms[mb], fuse_mx ? PRE_EPI : PRE_NONE);
                 // ln2 backward + residual: dres2 = dres3 + LN2'(dln2); attproj_b += colsum(dres2)
                 after_wgrad(EV_W3, ms[mb]);  // the previous layer's attproj wgrad has read rbB
@@ -1394,8 +1473,9 @@ struct Trainer {
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d3;
-                d3.A = rbB + r0 * C; d3.lda = C; dgrad_b(d3, P_ATTPROJW, l, C, C);
-                d3.C = datty + r0 * C; d3.ldc = C; d3.M = (int)R; d3.N = C; d3.K = C; d3.epi = EPI_BF16_STORE;
+                d3.A = rbB + r0 * C; d3.lda = rs * C; dgrad_b(d3, P_ATTPROJW, l, C, C);
+                d3.C = datty + r0 * C; d3.ldc = rs * C; d3.M = Mr; d3.N = C; d3.K = C; d3.epi = EPI_BF16_STORE;
+                d3.rows_gathered = lcg;
                 gemm_w(TC_PROJ_DGRAD, d3, P_ATTPROJW, l, true, mb, ms[mb], lbm ? PRE_LN : PRE_NONE, false,
                        rc && !lbm ? &dcol[1] : nullptr, lbm ? -1 : EV_RESB);
                 // attention (+ qkv_b)
@@ -2435,6 +2515,8 @@ int vit_trainer_set_option(vit_trainer_t* h, const char* name, int value) {
         t.lnb_mx = value != 0;
     } else if (n == "clip_overlap") {  // gradient clipping: partial sums per chunk beside the backward (1), at step time (0), auto (-1)
         t.clip_overlap = value < 0 ? -1 : value != 0;
+    } else if (n == "last_cls") {  // bf16: the last block's row-wise ops after attention on the CLS rows only (default 1)
+        t.last_cls = value != 0;
     } else if (n == "dp_probe") {
         if (value && !t.dp_snap) {  // allocated once, kept until destroy
             t.dp_snap = t.alloc<float>(t.arena_elems);
