@@ -28,6 +28,7 @@
 #ifndef VIT_JPEG_H
 #define VIT_JPEG_H
 
+#include "vit_data.h"
 #include "vit_trainer.h"
 
 #ifdef __cplusplus
@@ -65,6 +66,15 @@ int vit_jpeg_loader_decode_u8(vit_jpeg_loader_t* l, unsigned char* dev_out, int 
  * (as vit_trainer_set_batch_u8: pixel = (u8 / 255 - mean[c]) / std[c]); decode on the trainer's
  * copy stream, ordered before the next forward. */
 int vit_trainer_set_batch_jpeg(vit_trainer_t* t, vit_jpeg_loader_t* l, const float* mean3, const float* std3);
+/* RandAugment (vit_data.h): num_ops = 0 switches it off (the default); 1..VIT_AUG_MAX_DEPTH ops of
+ * magnitude 0..30 switch it on for every later decode of the current batch (vit_jpeg_loader_decode_u8,
+ * vit_trainer_set_batch_jpeg): after the resize, on the same stream, image i gets
+ * vit_randaugment_draw(seed, epoch * N + record_i, num_ops, magnitude, img) — like the crops a
+ * function of (seed, epoch, record) only.  The crop and flip draws do not depend on it. */
+int vit_jpeg_loader_set_randaugment(vit_jpeg_loader_t* l, int num_ops, int magnitude, const unsigned char* fill3);
+/* The current batch's plan for images of img x img: plan [batch][depth] (nullable) and depth
+ * (0 = RandAugment off; nothing is written to plan then). */
+int vit_jpeg_loader_plan(const vit_jpeg_loader_t* l, int img, vit_aug_op_t* plan, int* depth);
 void vit_jpeg_loader_close(vit_jpeg_loader_t* l);
 
 #ifdef __cplusplus

@@ -63,6 +63,8 @@ enum {
     VIT_HIT_GEMM_PP = 88,            /* bf16 two-group ping-pong 192x256 engine (variant 11; also counted as 256x256 + epi) */
     VIT_HIT_LN_MX = 89,              /* LayerNorm forward straight into the row + column MX forms (fp8) */
     VIT_HIT_LNB_MX = 90,             /* LayerNorm backward (residual-gradient stream) + both MX forms (fp8) */
+    VIT_HIT_AUGMENT = 91,            /* RandAugment on the uint8 batch: + 0 statistics / LUT, 1 in-place apply,
+                                        2 out-of-place apply (sharpness, affine), 3 copy back */
     VIT_HIT_COUNT = 96
 };
 int vit_kernel_hits(long long* out, int n); /* copies min(n, VIT_HIT_COUNT); returns VIT_HIT_COUNT */

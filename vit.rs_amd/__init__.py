@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("VIT_LIB") or os.path.join(HERE, "libvit_hip.so")  # V
 from . import data  # noqa: E402  (configs, canonical layout, seeded synthetic inputs)
 from . import mix  # noqa: E402  (mixup / cutmix draws and their numpy statement)
 from . import groups  # noqa: E402  (parameter-group tables: no_decay, layer_decay)
+from . import augment  # noqa: E402  (RandAugment: the policy draw and its numpy statement)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
@@ -163,6 +164,9 @@ _SIGS = {
     "vit_loader_num_records": (LL, [P]), "vit_loader_steps_per_epoch": (I, [P]),
     "vit_loader_next": (I, [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(LL), ctypes.POINTER(I)]),
     "vit_trainer_set_batch_u8": (I, [P, P, P, P, P]),
+    "vit_augment_u8": (I, [P, I, I, P, I, P, P]),
+    "vit_randaugment_draw": (I, [ctypes.c_ulonglong, LL, I, I, I, P]),
+    "vit_trainer_set_augment_plan": (I, [P, P, I, P]),
     # JPEG input pipeline (include/vit_jpeg.h)
     "vit_jpeg_probe": (I, [P, LL, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)]),
     "vit_jpeg_coefficients": (I, [P, LL, P, LL, P]),
@@ -173,6 +177,8 @@ _SIGS = {
     "vit_jpeg_loader_boxes": (I, [P, P]),
     "vit_jpeg_loader_decode_u8": (I, [P, P, I]),
     "vit_trainer_set_batch_jpeg": (I, [P, P, P, P]),
+    "vit_jpeg_loader_set_randaugment": (I, [P, I, I, P]),
+    "vit_jpeg_loader_plan": (I, [P, I, P, ctypes.POINTER(I)]),
     "vit_trainer_save_checkpoint": (I, [P, ctypes.c_char_p]),
     "vit_trainer_load_checkpoint": (I, [P, ctypes.c_char_p]),
 }
@@ -213,6 +219,7 @@ HIT_ATTN_BWD_XKEY, HIT_QUANT_ROWCOL = 86, 87
 HIT_GEMM_PP = 88
 HIT_LN_MX = 89
 HIT_LNB_MX = 90
+HIT_AUGMENT = 91  # + 0 statistics / LUT, 1 in-place apply, 2 out-of-place apply, 3 copy back
 
 
 def kernel_hits():
@@ -313,6 +320,22 @@ def call(name, *args):
     getattr(L, name)(*cargs)
     L.vit_sync()
     check(name)
+
+
+def augment_u8(images, plan, fill=(0, 0, 0)):
+    """Apply a RandAugment plan [batch][depth] (augment.op tuples) in place to a DeviceArray uint8
+    [batch, img, img, 3] on the context stream (vit_augment_u8); synchronous."""
+    assert images.dtype == np.uint8 and len(images.shape) == 4 and images.shape[3] == 3
+    assert images.shape[1] == images.shape[2]
+    arr, batch, depth = augment.plan_to_c(plan)
+    assert batch == images.shape[0]
+    f = (ctypes.c_ubyte * 3)(*fill)
+    if lib().vit_augment_u8(images.ptr, batch, images.shape[1], arr, depth, f, None):
+        check("vit_augment_u8")
+        raise VitError("vit_augment_u8 failed")
+    lib().vit_sync()
+    check("vit_augment_u8")
+    return images
 
 
 # --------------------------------------------------------------------------- checkpoints
@@ -489,6 +512,23 @@ class JpegLoader:
             check("vit_jpeg_loader_decode_u8")
         return out
 
+    def set_randaugment(self, num_ops=2, magnitude=9, fill=(0, 0, 0)):
+        """RandAugment(num_ops, magnitude) on every later decode of the current batch (after the
+        resize, on the device); num_ops 0 switches it off (vit_jpeg_loader_set_randaugment)."""
+        f = (ctypes.c_ubyte * 3)(*fill)
+        if lib().vit_jpeg_loader_set_randaugment(self.h, int(num_ops), int(magnitude), f):
+            check("vit_jpeg_loader_set_randaugment")
+            raise VitError("vit_jpeg_loader_set_randaugment failed")
+
+    def plan(self, img):
+        """The current batch's RandAugment plan [B][depth] for img x img images ([] when off)."""
+        depth = I()
+        arr = (augment.AugOp * (self.B * augment.MAX_DEPTH))()
+        if lib().vit_jpeg_loader_plan(self.h, int(img), arr, ctypes.byref(depth)):
+            check("vit_jpeg_loader_plan")
+            raise VitError("vit_jpeg_loader_plan failed")
+        return augment.plan_from_c(arr, self.B, depth.value) if depth.value else []
+
     def close(self):
         if getattr(self, "h", None):
             lib().vit_jpeg_loader_close(self.h)
@@ -603,6 +643,18 @@ class ViT:
         sd = np.ascontiguousarray(std, np.float32)
         self._ok(lib().vit_trainer_set_batch_u8(self.h, iptr, lptr, m.ctypes.data_as(P),
                                                 sd.ctypes.data_as(P)), "set_batch_u8")
+
+    def set_augment_plan(self, plan, fill=(0, 0, 0)):
+        """One-shot RandAugment plan [B][depth] for the next set_batch_u8 only (applied on the device
+        between the upload and the normalise); None clears a pending plan
+        (vit_trainer_set_augment_plan)."""
+        f = (ctypes.c_ubyte * 3)(*fill)
+        if plan is None:
+            self._ok(lib().vit_trainer_set_augment_plan(self.h, None, 0, f), "set_augment_plan")
+            return
+        arr, batch, depth = augment.plan_to_c(plan)
+        assert batch == self.B
+        self._ok(lib().vit_trainer_set_augment_plan(self.h, arr, depth, f), "set_augment_plan")
 
     def set_label_smoothing(self, eps):
         """0 <= eps < 1; persists across batches (vit_trainer_set_label_smoothing)."""

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/vit_jpeg.h"
+#include "augment.h"
 #include "jpeg_internal.h"
 
 namespace vit {
@@ -262,6 +263,7 @@ struct HostBatch {
     int max_blk = 0;
     std::vector<int> labels;
     std::vector<int> boxes;  // [n][5]
+    std::vector<long long> recs;  // [n] record numbers (the key of the per-record draws)
     std::vector<long long> img_bb, img_vb;  // first block / value of each image
     long long epoch = 0;
     int step = 0;
@@ -431,6 +433,9 @@ struct DeviceSide {
     size_t pcap = 0;
     hipEvent_t done = nullptr;      // the kernels of the previous batch (buffer reuse across streams)
     hipEvent_t uploaded = nullptr;  // the upload of the current batch (pinned host block reusable)
+    vit::aug::Prepared aug_plan;    // RandAugment of the batch in flight (read by its upload)
+    void* ascratch = nullptr;
+    size_t acap = 0;
 
     bool grow(void** p, size_t& cap, size_t need) {
         if (need <= cap) return true;
@@ -450,13 +455,18 @@ struct DeviceSide {
         return true;
     }
     // enqueue the upload and both kernels of hb on st; out [n][img][img][3] uint8 (device)
-    bool run(const HostBatch& hb, uint8_t* out, int img, hipStream_t st) {
+    // (augment: apply aug_plan, prepared by the caller, after the resize)
+    bool run(const HostBatch& hb, uint8_t* out, int img, hipStream_t st, bool augment) {
         if ((!done && hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) ||
             (!uploaded && hipEventCreateWithFlags(&uploaded, hipEventDisableTiming) != hipSuccess)) {
             set_error("jpeg: event creation failed");
             return false;
         }
         if (!grow((void**)&dbuf, dcap, hb.used) || !grow((void**)&planes, pcap, (size_t)std::max<long long>(hb.plane_bytes, 1))) {
+            set_error("jpeg: device allocation failed");
+            return false;
+        }
+        if (augment && !grow(&ascratch, acap, vit::aug::scratch_bytes(hb.n, img))) {
             set_error("jpeg: device allocation failed");
             return false;
         }
@@ -471,6 +481,7 @@ struct DeviceSide {
             planes, desc, reinterpret_cast<const uint64_t*>(dbuf + hb.o_mask),
             reinterpret_cast<const uint32_t*>(dbuf + hb.o_voff), reinterpret_cast<const int16_t*>(dbuf + hb.o_vals));
         color_resize_k<<<dim3((img * img + 255) / 256, hb.n), 256, 0, st>>>(out, img, planes, desc);
+        if (augment && !vit::aug::enqueue(aug_plan, out, ascratch, st)) return false;
         if (hipGetLastError() != hipSuccess || hipEventRecord(done, st) != hipSuccess) {
             set_error("jpeg: kernel launch failed");
             return false;
@@ -484,6 +495,7 @@ struct DeviceSide {
         if (uploaded) (void)hipEventDestroy(uploaded);
         if (dbuf) (void)hipFree(dbuf);
         if (planes) (void)hipFree(planes);
+        if (ascratch) (void)hipFree(ascratch);
     }
 };
 
@@ -543,6 +555,17 @@ struct vit_jpeg_loader {
     bool job_copy = false;
     std::vector<ImgOut> outs;
     DeviceSide dev;
+    // RandAugment (vit_jpeg_loader_set_randaugment): drawn per decode from (seed, epoch, record)
+    int ra_ops = 0, ra_mag = 0;
+    unsigned char ra_fill[3]{};
+
+    bool batch_plan(const HostBatch& hb, int img, vit_aug_op_t* plan) const {
+        for (int b = 0; b < hb.n; b++)
+            if (vit_randaugment_draw(seed, hb.epoch * N + hb.recs[(size_t)b], ra_ops, ra_mag, img,
+                                     plan + (size_t)b * ra_ops))
+                return false;
+        return true;
+    }
 
     void make_perm(long long epoch) {
         perm.resize((size_t)N);
@@ -626,6 +649,7 @@ struct vit_jpeg_loader {
                 crop_box(o.f.w, o.f.h, augment, seed ^ sm64(0x6a70656755ULL, (uint64_t)(epoch * N + r)), &hb.boxes[(size_t)b * 5]);
         }
         if (assemble(hb, outs, B, hb.boxes.data())) pool_job(nullptr, &hb);
+        hb.recs = recs;
         hb.epoch = epoch;
         hb.step = step;
     }
@@ -688,7 +712,16 @@ bool jpeg_loader_decode_to(vit_jpeg_loader_t* l, uint8_t* out, int img, hipStrea
         return false;
     }
     if (labels) *labels = hb->labels.data();
-    return l->dev.run(*hb, out, img, st);
+    const bool augment = l->ra_ops > 0;
+    if (augment) {
+        // the previous decode's upload reads dev.aug_plan: it has run once that decode is done
+        if (l->dev.done) (void)hipEventSynchronize(l->dev.done);
+        std::vector<vit_aug_op_t> plan((size_t)hb->n * l->ra_ops);
+        if (!l->batch_plan(*hb, img, plan.data()) ||
+            !aug::prepare(plan.data(), hb->n, img, l->ra_ops, l->ra_fill, "jpeg loader randaugment", l->dev.aug_plan))
+            return false;
+    }
+    return l->dev.run(*hb, out, img, st, augment);
 }
 }  // namespace vit
 
@@ -824,6 +857,28 @@ int vit_jpeg_loader_boxes(const vit_jpeg_loader_t* l, int* boxes) {
     const HostBatch& s = l->slots[(size_t)l->out_slot];
     memcpy(boxes, s.boxes.data(), s.boxes.size() * sizeof(int));
     return 0;
+}
+
+int vit_jpeg_loader_set_randaugment(vit_jpeg_loader_t* l, int num_ops, int magnitude, const unsigned char* fill3) {
+    if (!l || num_ops < 0 || num_ops > VIT_AUG_MAX_DEPTH || (num_ops > 0 && (magnitude < 0 || magnitude > 30 || !fill3))) {
+        set_error("vit_jpeg_loader_set_randaugment: bad arguments (num_ops %d of 0..%d, magnitude %d of 0..30)", num_ops,
+                  VIT_AUG_MAX_DEPTH, magnitude);
+        return 1;
+    }
+    l->ra_ops = num_ops;
+    l->ra_mag = num_ops ? magnitude : 0;
+    if (num_ops) memcpy(l->ra_fill, fill3, 3);
+    return 0;
+}
+
+int vit_jpeg_loader_plan(const vit_jpeg_loader_t* l, int img, vit_aug_op_t* plan, int* depth) {
+    if (!l || l->out_slot < 0 || !depth) {
+        set_error("vit_jpeg_loader_plan: no current batch");
+        return 1;
+    }
+    *depth = l->ra_ops;
+    if (!l->ra_ops || !plan) return 0;
+    return l->batch_plan(l->slots[(size_t)l->out_slot], img, plan) ? 0 : 1;
 }
 
 int vit_jpeg_loader_decode_u8(vit_jpeg_loader_t* l, unsigned char* dev_out, int img) {

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "augment.h"
 #include "ops_internal.h"
 #include "../../include/vit_trainer.h"
 #include "../../include/vit_checkpoint.h"
@@ -370,6 +371,10 @@ struct Trainer {
     int* lab_stage[2]{};
     hipEvent_t u8_copied[2]{}, u8_used[2]{};
     int u8_k = 0;
+    // one-shot RandAugment plan for the next set_batch_u8 (augment.hip)
+    aug::Prepared aug_plan;
+    bool aug_pending = false;
+    void* aug_scratch = nullptr;
     // AdamW state (allocated on the first AdamW step / a checkpoint load with optimizer state)
     float *adam_m = nullptr, *adam_v = nullptr;
     int adam_t = 0;
@@ -1835,6 +1840,10 @@ struct Trainer {
             if (!jpeg_loader_decode_to(jl, u8_stage[k], cfg.img, s_copy, &lab, B)) return false;
         } else {
             VIT_HIP(hipMemcpyAsync(u8_stage[k], img, bytes, hipMemcpyHostToDevice, s_copy));
+            if (aug_pending) {  // between the upload and the normalise, on the copy stream; the
+                aug_pending = false;  // host waits for u8_copied below, so the plan has been read
+                if (!aug::enqueue(aug_plan, u8_stage[k], aug_scratch, s_copy)) return false;
+            }
         }
         if (lab) VIT_HIP(hipMemcpyAsync(lab_stage[k], lab, (size_t)B * 4, hipMemcpyHostToDevice, s_copy));
         VIT_HIP(hipEventRecord(u8_copied[k], s_copy));
@@ -1849,6 +1858,20 @@ struct Trainer {
         // the host buffers may be reused once the DMA has read them (overlaps the GPU's queue)
         VIT_HIP(hipEventSynchronize(u8_copied[k]));
         return !has_error();
+    }
+
+    bool set_augment_plan(const vit_aug_op_t* plan, int depth, const unsigned char* fill3) {
+        if (!plan) {
+            aug_pending = false;
+            return true;
+        }
+        aug::Prepared p;
+        if (!aug::prepare(plan, B, cfg.img, depth, fill3, "vit_trainer_set_augment_plan", p)) return false;
+        if (!aug_scratch) aug_scratch = alloc<unsigned char>((long long)aug::scratch_bytes(B, cfg.img));
+        if (!aug_scratch) return false;
+        aug_plan = std::move(p);
+        aug_pending = true;
+        return true;
     }
 
     bool ensure_adam() {
@@ -2269,6 +2292,14 @@ int vit_trainer_set_batch_u8(vit_trainer_t* h, const unsigned char* images, cons
     }
     if (labels && !labels_ok(labels, h->t.B, h->t.NC)) return 1;
     return h->t.set_batch_u8(images, labels, mean3, std3) ? 0 : 1;
+}
+int vit_trainer_set_augment_plan(vit_trainer_t* h, const vit_aug_op_t* host_plan, int depth,
+                                 const unsigned char* fill3) {
+    if (!h) {
+        set_error("vit_trainer_set_augment_plan: null trainer");
+        return 1;
+    }
+    return h->t.set_augment_plan(host_plan, depth, fill3) ? 0 : 1;
 }
 int vit_trainer_step_adamw(vit_trainer_t* h, float lr, float beta1, float beta2, float eps,
                            float weight_decay) {
