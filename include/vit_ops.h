@@ -189,6 +189,14 @@ void gelu_backward_bf16(float* dinp, const uint16_t* inp, const uint16_t* dout, 
 void gemm_bf16_ex(void* C, long long ldc, const uint16_t* A, long long lda, int a_kcontig,
                   const uint16_t* B, long long ldb, int b_kcontig, const float* bias,
                   float* dbias, int M, int N, int K, int epi, int splitk);
+/* gemm_bf16_ex (no bias / dbias) with the caller's promise that rows k of an M-contiguous A with
+ * k % k_period != 0 are exact zeros (k_period 0: none).  The split-K weight-gradient engine
+ * (epi 2, M-contiguous A, N-contiguous B, K % 32 == 0, M >= 256, N >= 128) then skips the 32-row
+ * K-steps that hold no row i * k_period when k_period > 32; the result has the bits of the dense
+ * call.  Every other engine and period runs dense. */
+void gemm_bf16_kperiod(void* C, long long ldc, const uint16_t* A, long long lda, int a_kcontig,
+                       const uint16_t* B, long long ldb, int b_kcontig, int M, int N, int K, int epi,
+                       int splitk, int k_period);
 /* the fused epilogues of the trainer's GEMMs: epi 4 C = pre = acc + bias, C2 = gelu(pre)
  * (both bf16); 5 C_f32 = acc + bias + aux_f32; 6 C_bf16 = acc * gelu'(aux_bf16) and, when
  * colsum_out is not NULL, colsum_out[n] += sum_m C[m][n]; 0 / 3 as gemm_bf16_ex.  The pair the
@@ -199,6 +207,15 @@ void gemm_bf16_fused(void* C, void* C2, long long ldc, const void* aux, long lon
                      const uint16_t* A, long long lda, int a_kcontig, const uint16_t* B,
                      long long ldb, int b_kcontig, const float* bias, float* colsum_out, int M,
                      int N, int K, int epi);
+/* gemm_bf16_fused on a strided selection of rows (lda / ldc / ldaux = a multiple of the dense pitch).
+ * rows_gathered: the call keeps the 256x256 engine of the dense tensor's other GEMMs for any M >= 1
+ * (N >= 256, K % 64 == 0, K-contiguous A).  colsum_row_period = p > 0 (epi 6 / 9 of such a call, p >= 128,
+ * N % 8 == 0; an error otherwise): output row m is row m * p of a dense tensor whose other rows are
+ * exact zeros, and colsum_out receives what the dense M * p row call would add, bit for bit. */
+void gemm_bf16_fused_rows(void* C, void* C2, long long ldc, const void* aux, long long ldaux,
+                          const uint16_t* A, long long lda, int a_kcontig, const uint16_t* B,
+                          long long ldb, int b_kcontig, const float* bias, float* colsum_out, int M,
+                          int N, int K, int epi, int rows_gathered, int colsum_row_period);
 /* ------------------------------------------------------------------ fp8 (MXFP8) GEMM path
  * OCP fp8 e4m3 operands with one E8M0 scale per 32 consecutive k-elements of a row (OCP MX block
  * scaling) on v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulate: the fp8 mode's forward and

@@ -200,6 +200,10 @@ int vit_trainer_set_concurrency(vit_trainer_t* t, int on);
  *      only the CLS row of each image, so the last block's attention projection, LayerNorm 2, fc + GELU
  *      and fcproj and the fc / attention-projection input gradients run on the B CLS rows instead of all
  *      B*T (same loss, logits and gradients bit for bit).  0: every row,
+ *      "last_cls_bwd" = 2 (default; honoured with last_cls on): 1 = the last block's three weight
+ *      gradients skip the K-steps of the token axis that hold no CLS row, 2 = also its fcproj input
+ *      gradient on the CLS rows, the fc-bias column sums kept in the full-size grouping (same bits
+ *      again).  0: both full size,
  *      "dp_probe" = 1: every gradient chunk is also copied, on the all-reduce stream right after
  *      its all-reduce, into a snapshot arena (read with vit_trainer_get_dp_snapshot) — a check
  *      that each overlapped chunk was final when it was reduced.

@@ -107,7 +107,9 @@ _SIGS = {
     "gelu_forward_bf16": (None, [P, P, I]),
     "gelu_backward_bf16": (None, [P, P, P, I]),
     "gemm_bf16_ex": (None, [P, LL, P, LL, I, P, LL, I, P, P, I, I, I, I, I]),
+    "gemm_bf16_kperiod": (None, [P, LL, P, LL, I, P, LL, I, I, I, I, I, I, I]),
     "gemm_bf16_fused": (None, [P, P, LL, P, LL, P, LL, I, P, LL, I, P, P, I, I, I, I]),
+    "gemm_bf16_fused_rows": (None, [P, P, LL, P, LL, P, LL, I, P, LL, I, P, P, I, I, I, I, I, I]),
     "mx_scale_size": (LL, [LL, I]),
     "quantize_mx_bf16_ex": (None, [P, P, P, LL, I, LL, LL]),
     "quantize_mx_f32_ex": (None, [P, P, P, LL, I, LL, LL]),

@@ -25,9 +25,15 @@ enum Epi {
     // epilogue is one multiply instead of a second sigmoid (exp + rcp) per element
     EPI_BF16_GELU_D = 8,  // C_bf16 = gelu'(pre), pre = acc + bias; C2_bf16 = gelu(pre)
     EPI_BF16_MUL = 9,     // C_bf16 = acc * aux_bf16[m*ldaux + n]   (aux = a stored gelu')
+    // internal: EPI_BF16_DGELU / _MUL of a colsum_row_period call (the column sums stored per row).  Kernel
+    // instances of their own, so the dense epilogues keep their code and registers
+    EPI_BF16_DGELU_ROWS = 10,
+    EPI_BF16_MUL_ROWS = 11,
 };
 // epilogues that read a bf16 aux operand / that may sum the output's columns (colsum_out)
-constexpr bool epi_aux16(int e) { return e == EPI_BF16_DGELU || e == EPI_BF16_MUL; }
+constexpr bool epi_rows(int e) { return e == EPI_BF16_DGELU_ROWS || e == EPI_BF16_MUL_ROWS; }
+constexpr bool epi_aux16(int e) { return e == EPI_BF16_DGELU || e == EPI_BF16_MUL || epi_rows(e); }
+constexpr bool epi_dgelu(int e) { return e == EPI_BF16_DGELU || e == EPI_BF16_DGELU_ROWS; }  // (else: x aux)
 // epilogues that add the bias
 constexpr bool epi_bias(int e) { return e != EPI_F32_ATOMIC && e != EPI_F32_SLAB && !epi_aux16(e); }
 // epilogues with an MX copy of a bf16 output (gelu for the GELU pairs, the product for the aux ones)
@@ -61,6 +67,12 @@ struct GemmArgs {
     // (0 = the engine's default, 45: a weight gradient beside other streams; the trainer passes 80 when
     // the kernel has the GPU to itself)
     int fill_pct = 0;
+    // the caller's promise for an M-contiguous A: rows k with k % k_period != 0 are exact zeros (0 = dense).
+    // The 256x128 split-K engine then walks only the 32-row K-steps that hold a row i * k_period (when
+    // k_period > 32), with the dense call's split count, slabs and reduce: the skipped steps would add
+    // products of exact zeros to fp32 accumulators that are never -0, so the result keeps its bits.
+    // Every other engine, and a smaller period, runs dense.  B must be finite in the steps read.
+    int k_period = 0;
     // gemm_bf16, row-gathered calls (the trainer's last block): the M rows are a strided
     // selection (lda / ldc / ldaux = a multiple of the dense pitch) of a tensor whose other GEMMs run on
     // the persistent 256x256 engine, so the call keeps that engine for any M >= 1 (one ragged row panel:
@@ -69,6 +81,14 @@ struct GemmArgs {
     // K % 64 == 0, K-contiguous A, no split-K; the persistent form for a K-contiguous B within the
     // 2^31-byte operand spans, else the one-tile form); every other call dispatches as without it.
     bool rows_gathered = false;
+    // x-aux epilogues (EPI_BF16_DGELU / _MUL) of a row-gathered call on the 256x256 engines: output row m is
+    // row m * colsum_row_period of the dense tensor, whose other rows are exact zeros the call leaves out.
+    // The column sums keep the dense call's partial-row layout (cdiv(M * period, 128) rows, gemm_colsum_rows):
+    // each row's products are stored as 0.f + v into partial row (m * period) >> 7, which is what the dense
+    // call's sum over that row's 128-row block gives, bit for bit.  The partial rows must be zero before the
+    // call (the launcher clears its own workspace; a caller's colsum_part is the caller's to clear).
+    // period >= 128 (one row per block: one writer per element), N % 8 == 0; gemm_colsum_period_ok.
+    int colsum_row_period = 0;
     // split-K workspace for EPI_F32_ATOMIC on the 256x256 kernel: partials go to fp32 slabs and
     // one reduce kernel adds them into C (no atomics).  nullptr = the calling thread's workspace
     // (ordered on the context stream); the trainer passes its own buffer for its stream.
@@ -102,6 +122,12 @@ void gemm_f32(const GemmArgs& a, hipStream_t s);
 // operands, lda/ldb%8==0, the contiguous dim of an M/N-contig operand %8==0, N%4==0.
 void gemm_bf16(const GemmArgs& a, hipStream_t s);
 bool gemm_bf16_supported(const GemmArgs& a);
+// gemm_bf16 takes the call on the 256x128 split-K engine and honours its k_period there
+bool gemm_bf16_kskip(const GemmArgs& a);
+// gemm_bf16 accepts the call's colsum_row_period (it rejects the call otherwise): an x-aux epilogue of a
+// row-gathered call that stays on the 256x256 LDS-DMA engines (not the ping-pong engine of variant 11,
+// whose partial rows are 96 tall), period >= 128, N % 8 == 0
+bool gemm_colsum_period_ok(const GemmArgs& a);
 // engine selection for A/B measurements in one process: 1 = 128x128 everywhere, 2 = 256x256, 1 WG/CU,
 // one tile per workgroup (split-K weight gradients on 256x128, 2 WG/CU), 7 = production: as 2 with
 // the persistent streaming 256x256 engine, 11 = as 7 with the ping-pong 192x256 engine for the shapes

@@ -768,7 +768,12 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmParams p) {
     const int tm0 = tm * BM, tn0 = tn * BN;
     const int kbeg = split * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);
-    const int nk = (kend - kbeg) / BK;
+    // k_period (GemmArgs::k_period, > BK): rows k % k_period != 0 of A are exact zeros, so only the
+    // 32-row K-steps of [kbeg, kend) that hold a row i * k_period run, in ascending order: the dense
+    // loop's own steps (kbeg, kend and the step bases are multiples of BK), at most one period row each
+    const int kper = p.k_period;
+    const int i0 = kper > 0 ? (kbeg + kper - 1) / kper : 0;
+    const int nk = kper > 0 ? max((kend + kper - 1) / kper - i0, 0) : (kend - kbeg) / BK;
     const bf16_t* A = (const bf16_t*)p.A;
     const bf16_t* B = (const bf16_t*)p.B;
 
@@ -780,7 +785,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmParams p) {
 
     auto issue = [&](int st) {
         char* sl = smem + (st % NSLOT) * SLOT_BYTES;
-        const int k0 = kbeg + st * BK;
+        const int k0 = kper > 0 ? ((i0 + st) * kper) & ~(BK - 1) : kbeg + st * BK;
         stage<BM>(A, p.lda, tm0, p.M, k0, sl, wave, lane);
         stage<BN>(B, p.ldb, tn0, p.N, k0, sl + A_BYTES, wave, lane);
     };
@@ -1048,7 +1053,10 @@ static bool pp_taken(const GemmArgs& a) {
     return gemm_variant() == 11 && !a.a_scale && a.epi != EPI_F32_ATOMIC && gemm_bf16_supported(a) &&
            a.K % g2::KTILE == 0 && a.M >= 256 && a.N >= 256 && (a.N <= 1280 || pp_all()) && gemm_pp_shape(a);
 }
-int gemm_colsum_rows(const GemmArgs& a, bool fp8) { return cdiv(a.M, !fp8 && pp_taken(a) ? 96 : 128); }
+int gemm_colsum_rows(const GemmArgs& a, bool fp8) {
+    if (!fp8 && a.colsum_row_period > 0) return cdiv((long long)a.M * a.colsum_row_period, 128);  // the dense layout
+    return cdiv(a.M, !fp8 && pp_taken(a) ? 96 : 128);
+}
 float* colsum_rows_begin(const GemmArgs& a) {
     if (!epi_aux16(a.epi) || !(a.colsum_out || a.colsum_part)) return nullptr;
     float* r = a.colsum_part ? a.colsum_part
@@ -1169,6 +1177,8 @@ GemmParams make_gemm_params(const GemmArgs& a, int kchunk) {
     p.mxc_off = (int)a.mxc_off;
     p.mxc_rg = (int)(mx_rows_padded(a.N) / 32);
     p.tiles = 1;
+    p.k_period = 0;  // (the 256x128 launcher sets it)
+    p.colsum_row_period = 0;  // (gemm_bf16 sets it on the 256x256 engines)
     return p;
 }
 
@@ -1301,10 +1311,21 @@ static void launch_g2(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStre
                 VIT_CASE(EPI_BF16_DGELU)
                 VIT_CASE(EPI_BF16_GELU_D)
                 VIT_CASE(EPI_BF16_MUL)
+                VIT_CASE(EPI_BF16_DGELU_ROWS)
+                VIT_CASE(EPI_BF16_MUL_ROWS)
 #undef VIT_CASE
                 default: break;
             }
         }
+    }
+    if (epi_rows(a.epi)) {  // (row-gathered calls: K-contiguous A only)
+        if constexpr (AK) {
+            if (a.epi == EPI_BF16_MUL_ROWS) g2::gemm_kernel<AK, BKC, EPI_BF16_MUL_ROWS, 2><<<grid, g2::NT, 0, s>>>(p);
+            else g2::gemm_kernel<AK, BKC, EPI_BF16_DGELU_ROWS, 2><<<grid, g2::NT, 0, s>>>(p);
+        } else {
+            set_error("gemm_bf16: colsum_row_period needs a K-contiguous A");
+        }
+        return;
     }
     switch (a.epi) {
 #define VIT_CASE(E) \
@@ -1386,6 +1407,9 @@ static void gemm_bf16_g4(const GemmArgs& a, hipStream_t s) {
     }
     GemmParams p = make_gemm_params(b, kchunk);
     p.tiles = tiles;
+    // K-step skipping: the split count, kchunk, slabs and grid above are the dense call's; a period of
+    // at most one K-step skips nothing and runs dense
+    p.k_period = a.k_period > g4::BK ? a.k_period : 0;
     dim3 grid(tiles, split);
     if (slab) g4::gemm_kernel<EPI_F32_SLAB><<<grid, g4::NT, 0, s>>>(p);
     else g4::gemm_kernel<EPI_F32_ACC><<<grid, g4::NT, 0, s>>>(p);
@@ -1395,6 +1419,26 @@ static void gemm_bf16_g4(const GemmArgs& a, hipStream_t s) {
     // bias gradient (A = dout^T): column sums of dout over the K rows (the thread workspace may be
     // the slab just reduced: stream-ordered after the reduce)
     if (a.dbias) colsum_bf16(a.dbias, (const bf16_t*)a.A, a.K, a.M, a.lda, s);
+}
+
+// split-K weight gradients (M/N-contiguous operands, K = the token count) run on the 256x128
+// two-per-CU engine: 3-9 % faster than 256x256 on every ViT-B/16 wgrad shape (r02,
+// tools/bench_gemm.py), the other GEMMs are faster on 256x256
+static bool g4_taken(const GemmArgs& a) {
+    return gemm_variant() != 1 && a.epi == EPI_F32_ATOMIC && !a.a_kcontig && !a.b_kcontig &&
+           a.K % g4::KTILE == 0 && a.M >= 256 && a.N >= 128 && a.N % 4 == 0 &&
+           (a.splitk > 0 || !a.ws ||
+            (size_t)choose_split_g4(cdiv(a.M, g4::BM) * cdiv(a.N, g4::BN), a.K / g4::KTILE, a.fill_pct) * a.M * a.N *
+                    sizeof(float) <= a.ws_bytes);
+}
+bool gemm_bf16_kskip(const GemmArgs& a) {
+    return a.M > 0 && a.N > 0 && !a.mx_q && !a.mxc_q && gemm_bf16_supported(a) && g4_taken(a) && a.k_period > g4::BK;
+}
+bool gemm_colsum_period_ok(const GemmArgs& a) {
+    return epi_aux16(a.epi) && a.colsum_row_period >= 128 && (a.colsum_out || a.colsum_part) &&
+           a.rows_gathered && a.M >= 1 && a.a_kcontig && a.K % g2::KTILE == 0 && a.N >= 256 && a.N % 8 == 0 &&
+           gemm_variant() != 1 && gemm_variant() != 11 && !a.mx_q && !a.mxc_q && gemm_bf16_supported(a) &&
+           (long long)a.M * a.colsum_row_period < (1LL << 31) && ((uintptr_t)a.colsum_part & 15) == 0;  // (16-B row stores)
 }
 
 void gemm_bf16(const GemmArgs& a, hipStream_t s) {
@@ -1408,14 +1452,16 @@ void gemm_bf16(const GemmArgs& a, hipStream_t s) {
                   a.M, a.N, a.K, a.lda, a.ldb);
         return;
     }
-    // split-K weight gradients (M/N-contiguous operands, K = the token count) run on the 256x128
-    // two-per-CU engine: 3-9 % faster than 256x256 on every ViT-B/16 wgrad shape (r02,
-    // tools/bench_gemm.py), the other GEMMs are faster on 256x256
-    if (gemm_variant() != 1 && a.epi == EPI_F32_ATOMIC && !a.a_kcontig && !a.b_kcontig &&
-        a.K % g4::KTILE == 0 && a.M >= 256 && a.N >= 128 && a.N % 4 == 0 &&
-        (a.splitk > 0 || !a.ws ||
-         (size_t)choose_split_g4(cdiv(a.M, g4::BM) * cdiv(a.N, g4::BN), a.K / g4::KTILE) * a.M * a.N * sizeof(float) <=
-             a.ws_bytes)) {
+    if (epi_rows(a.epi)) {
+        set_error("gemm_bf16: epilogue %d is internal (colsum_row_period)", a.epi);
+        return;
+    }
+    if (a.colsum_row_period != 0 && !gemm_colsum_period_ok(a)) {
+        set_error("gemm_bf16: colsum_row_period %d needs a row-gathered x-aux call on the 256x256 engine, "
+                  "period >= 128, N %% 8 == 0 (M=%d N=%d K=%d epi=%d)", a.colsum_row_period, a.M, a.N, a.K, a.epi);
+        return;
+    }
+    if (g4_taken(a)) {
         gemm_bf16_g4(a, s);
         return;
     }
@@ -1448,6 +1494,12 @@ void gemm_bf16(const GemmArgs& a, hipStream_t s) {
         float* cs_rows = colsum_rows_begin(a);
         if ((a.colsum_out || a.colsum_part) && epi_aux16(a.epi) && !cs_rows) return;
         p.colsum_out = cs_rows;
+        if (a.colsum_row_period > 0) {  // (gemm_colsum_period_ok: an x-aux call that stays on this path, one split)
+            p.colsum_row_period = a.colsum_row_period;
+            b.epi = epi_dgelu(a.epi) ? EPI_BF16_DGELU_ROWS : EPI_BF16_MUL_ROWS;  // (counted as a.epi below)
+            if (!a.colsum_part)  // the launcher's own partial rows: only the gathered rows' blocks are written
+                VIT_HIP(hipMemsetAsync(cs_rows, 0, (size_t)gemm_colsum_rows(a, false) * a.N * sizeof(float), s));
+        }
         // fused bias gradient: one add per (column block, K-split), deterministic with one split
         const bool late_db = a.dbias && !a.a_kcontig && split > 1;
         if (late_db) p.dbias = nullptr;
@@ -1465,7 +1517,7 @@ void gemm_bf16(const GemmArgs& a, hipStream_t s) {
         else if (!a.a_kcontig && !a.b_kcontig) launch_g2<false, false>(b, p, grid, s);
         else launch_g2<false, true>(b, p, grid, s);
         after_launch("gemm_bf16_256");
-        count_hit(VIT_HIT_GEMM_256x256 + b.epi);
+        count_hit(VIT_HIT_GEMM_256x256 + (epi_rows(b.epi) ? a.epi : b.epi));
         if (slab) slab_reduce(a, slab, split, s);
         colsum_rows_end(a, cs_rows, s);
         if (late_db) colsum_bf16(a.dbias, (const bf16_t*)a.A, a.K, a.M, a.lda, s);

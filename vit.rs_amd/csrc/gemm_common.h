@@ -23,6 +23,11 @@ struct GemmParams {
     int stagger;  // two-per-CU engine: first-round delay (100 MHz ticks) of the CU's second workgroup
     unsigned long long* trace;  // diagnostic: [workgroup][4] start, main-loop end, end, hw id
     int tiles;   // output tiles of the launch (the grid is tiles x K-splits)
+    // the _ROWS x-aux epilogues (a row-gathered call with GemmArgs::colsum_row_period): output row m is row
+    // m * period of the dense tensor, and its products go, as 0.f + v, to partial row (m * period) >> 7
+    // of the pre-zeroed colsum_out instead of into the wave tile's sum
+    int colsum_row_period;
+    int k_period;  // 256x128 engine: > 0 = walk only the K-steps holding a row i * k_period (GemmArgs::k_period)
     int gm;      // persistent engine tile order: groups of gm row panels, column-major inside a group
                  // (0: row-major; VIT_GEMM_GM)
     uint8_t* mx_q;  // fused MX output (GemmArgs::mx_q / mx_s); mx_rg = padded rows / 32
@@ -213,7 +218,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, int m, int n, f32x
                                                         (long long)m * p.ldaux + n);
         const float x0 = __uint_as_float(h.x << 16), x1 = __uint_as_float(h.x & 0xffff0000u);
         const float x2 = __uint_as_float(h.y << 16), x3 = __uint_as_float(h.y & 0xffff0000u);
-        if constexpr (EPI == EPI_BF16_DGELU) {
+        if constexpr (epi_dgelu(EPI)) {
             v[0] *= gelu_grad_fast_f(x0); v[1] *= gelu_grad_fast_f(x1);
             v[2] *= gelu_grad_fast_f(x2); v[3] *= gelu_grad_fast_f(x3);
         } else {
@@ -298,7 +303,7 @@ __device__ __forceinline__ void epilogue8(const GemmParams& p, int m, int n, flo
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const float lo = __uint_as_float(hw[j] << 16), hi = __uint_as_float(hw[j] & 0xffff0000u);
-            if constexpr (EPI == EPI_BF16_DGELU) {
+            if constexpr (epi_dgelu(EPI)) {
                 v[2 * j] *= gelu_grad_fast_f(lo);
                 v[2 * j + 1] *= gelu_grad_fast_f(hi);
             } else {
@@ -306,8 +311,21 @@ __device__ __forceinline__ void epilogue8(const GemmParams& p, int m, int n, flo
                 v[2 * j + 1] *= hi;
             }
         }
+        if constexpr (epi_rows(EPI)) {
+            // the dense call summed this row with the exact zeros of its 128-row block into a sum that
+            // started at +0: 0.f + v (a -0 product gives +0).  The zero goes through a register the
+            // compiler cannot see into, so the add stays.  One writer per (partial row, column).
+            if (p.colsum_out) {
+                float z = 0.f;
+                asm volatile("" : "+v"(z));
+                float* q = p.colsum_out + (((long long)m * p.colsum_row_period) >> 7) * p.N + n;
+                reinterpret_cast<float4*>(q)[0] = make_float4(z + v[0], z + v[1], z + v[2], z + v[3]);
+                reinterpret_cast<float4*>(q)[1] = make_float4(z + v[4], z + v[5], z + v[6], z + v[7]);
+            }
+        } else {
 #pragma unroll
-        for (int j = 0; j < 8; j++) cs[j] += v[j];
+            for (int j = 0; j < 8; j++) cs[j] += v[j];
+        }
         }
         const uint4 d8 = pack8(v);
         if (p.C) *reinterpret_cast<uint4*>((bf16_t*)p.C + off) = d8;
@@ -437,7 +455,7 @@ __device__ __forceinline__ void staged_pass_interior(const GemmParams& p, const 
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const float lo = __uint_as_float(ax[it][j] << 16), hi = __uint_as_float(ax[it][j] & 0xffff0000u);
-                if constexpr (EPI == EPI_BF16_DGELU) {
+                if constexpr (epi_dgelu(EPI)) {
                     v[2 * j] *= gelu_grad_fast_f(lo);
                     v[2 * j + 1] *= gelu_grad_fast_f(hi);
                 } else {
@@ -529,6 +547,8 @@ __device__ __forceinline__ void mx_cols_pass(const GemmParams& p, const float* s
 }
 template <int EPI>
 __device__ __forceinline__ bool staged_interior(const GemmParams& p, int m0, int n0) {
+    // (a colsum_row_period call takes the row-by-row path for any M: its column sums are per row)
+    if constexpr (epi_rows(EPI)) return false;
     return EPI != EPI_F32_ATOMIC && m0 + 128 <= p.M && n0 + 64 <= p.N;
 }
 // fused bias gradient of the next GEMM: column sums of the DGELU / MUL output.  The wave's 128 x 64
@@ -536,7 +556,7 @@ __device__ __forceinline__ bool staged_interior(const GemmParams& p, int m0, int
 // (each (row, column) of the partial matrix has exactly one writer: no atomics, fixed order)
 template <int EPI>
 __device__ __forceinline__ void staged_colsum(const GemmParams& p, int lane, int m0, int n0, float (&cs)[8]) {
-    if constexpr (epi_aux16(EPI)) {
+    if constexpr (epi_aux16(EPI) && !epi_rows(EPI)) {
         if (p.colsum_out) {
             const int rr = lane >> 3, cc = (lane & 7) * 8;
 #pragma unroll
@@ -744,7 +764,7 @@ __device__ __forceinline__ void staged_pass_interior_q(const GemmParams& p, floa
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const float a0 = __uint_as_float(aux.ax[it][j] << 16), a1 = __uint_as_float(aux.ax[it][j] & 0xffff0000u);
-                if constexpr (EPI == EPI_BF16_DGELU) {
+                if constexpr (epi_dgelu(EPI)) {
                     v[2 * j] *= gelu_grad_fast_f(a0);
                     v[2 * j + 1] *= gelu_grad_fast_f(a1);
                 } else {

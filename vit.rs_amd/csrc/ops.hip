@@ -1317,6 +1317,18 @@ void gemm_bf16_ex(void* C, long long ldc, const uint16_t* A, long long lda, int 
     a.M = M; a.N = N; a.K = K; a.epi = epi; a.splitk = splitk;
     gemm_bf16(a, stream());
 }
+void gemm_bf16_kperiod(void* C, long long ldc, const uint16_t* A, long long lda, int a_kcontig,
+                       const uint16_t* B, long long ldb, int b_kcontig, int M, int N, int K, int epi,
+                       int splitk, int k_period) {
+    VIT_REQUIRE(epi >= EPI_F32_STORE && epi <= EPI_BF16_STORE, "gemm_bf16_kperiod: epi %d", epi);
+    VIT_REQUIRE(k_period >= 0, "gemm_bf16_kperiod: k_period %d", k_period);
+    GemmArgs a;
+    a.A = A; a.lda = lda; a.a_kcontig = a_kcontig != 0;
+    a.B = B; a.ldb = ldb; a.b_kcontig = b_kcontig != 0;
+    a.C = C; a.ldc = ldc;
+    a.M = M; a.N = N; a.K = K; a.epi = epi; a.splitk = splitk; a.k_period = k_period;
+    gemm_bf16(a, stream());
+}
 void gemm_bf16_fused(void* C, void* C2, long long ldc, const void* aux, long long ldaux,
                      const uint16_t* A, long long lda, int a_kcontig, const uint16_t* B,
                      long long ldb, int b_kcontig, const float* bias, float* colsum_out, int M,
@@ -1331,6 +1343,24 @@ void gemm_bf16_fused(void* C, void* C2, long long ldc, const void* aux, long lon
     a.C = C; a.C2 = C2; a.ldc = ldc; a.aux = aux; a.ldaux = ldaux; a.bias = bias;
     a.colsum_out = colsum_out;
     a.M = M; a.N = N; a.K = K; a.epi = epi;
+    gemm_bf16(a, stream());
+}
+void gemm_bf16_fused_rows(void* C, void* C2, long long ldc, const void* aux, long long ldaux,
+                          const uint16_t* A, long long lda, int a_kcontig, const uint16_t* B,
+                          long long ldb, int b_kcontig, const float* bias, float* colsum_out, int M,
+                          int N, int K, int epi, int rows_gathered, int colsum_row_period) {
+    VIT_REQUIRE(epi == EPI_BF16_GELU || epi == EPI_F32_RESID || epi == EPI_BF16_DGELU ||
+                    epi == EPI_F32_STORE || epi == EPI_BF16_STORE || epi == EPI_BF16_GELU_D ||
+                    epi == EPI_BF16_MUL,
+                "gemm_bf16_fused_rows: epi %d", epi);
+    VIT_REQUIRE(colsum_row_period >= 0, "gemm_bf16_fused_rows: colsum_row_period %d", colsum_row_period);
+    GemmArgs a;
+    a.A = A; a.lda = lda; a.a_kcontig = a_kcontig != 0;
+    a.B = B; a.ldb = ldb; a.b_kcontig = b_kcontig != 0;
+    a.C = C; a.C2 = C2; a.ldc = ldc; a.aux = aux; a.ldaux = ldaux; a.bias = bias;
+    a.colsum_out = colsum_out;
+    a.M = M; a.N = N; a.K = K; a.epi = epi;
+    a.rows_gathered = rows_gathered != 0; a.colsum_row_period = colsum_row_period;
     gemm_bf16(a, stream());
 }
 void gemm_bf16_set_variant(int variant) { gemm_set_variant(variant); }

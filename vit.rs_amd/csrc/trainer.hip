@@ -72,6 +72,16 @@ __global__ void add_cols_k(float* __restrict__ dst, const float* __restrict__ sr
         dst[i] += src[r * lds + (i - r * n)];
     }
 }
+// zero the 32-row blocks [(i * T) & ~31, + 32) of x [rows][n] (n % 8 == 0, 16-B aligned rows) for images
+// i < B: block (x, i) takes 16-B chunks x, x + gridDim.x, .. of image i's block
+__global__ void clear_cls_blocks_k(bf16_t* __restrict__ x, int T, long long rows, int n) {
+    const long long r0 = ((long long)blockIdx.y * T) & ~31LL;
+    const int cpr = n / 8;
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < 32 * cpr; c += gridDim.x * blockDim.x) {
+        const long long r = r0 + c / cpr;
+        if (r < rows) reinterpret_cast<uint4*>(x + r * n)[c % cpr] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
 __global__ void fill_k(float* p, float v, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -1075,15 +1085,60 @@ struct Trainer {
     // the row-wise ops after attention (attention projection, LayerNorm 2, fc + GELU, fcproj, and the fc /
     // attention-projection input gradients) run on the B CLS rows only, in place at row stride T in the
     // buffers of the full-size step.  bf16 mode only (fp32 is the parity path; the fp8 column forms span
-    // 32-token blocks).  The last block's three weight gradients stay full size, and so do the two
-    // kernels that take its small gradients' partial sums (the fcproj dgrad: fc_b; LayerNorm 2 backward:
-    // ln2_w, ln2_b, attproj_b), so every gradient keeps the full-size step's bits; the gradient rows the
-    // trimmed kernels no longer write are cleared once per step (last_cls_clear).
+    // 32-token blocks).  The last block's three weight gradients and the two kernels that take its small
+    // gradients' partial sums (the fcproj dgrad: fc_b; LayerNorm 2 backward: ln2_w, ln2_b, attproj_b) stay
+    // full size or (option last_cls_bwd, DESIGN.md §12.1: all but LayerNorm 2 backward) take forms that add
+    // the same values in the same order, so every gradient keeps the full-size step's bits; the gradient
+    // rows the trimmed kernels no longer write are cleared once per step (last_cls_clear).
     bool last_cls = true;    // option last_cls
+    // option last_cls_bwd (honoured with last_cls on): 1 = the last block's three weight gradients skip the
+    // K-steps without a CLS row (bit-identical: the skipped products are exact zeros), 0 = dense
+    // 2 (default) = also the last block's fcproj input gradient on the CLS rows, its fc-bias column sums
+    // stored per row into the partial rows of the full-size call (GemmArgs::colsum_row_period)
+    int lc_bwd = 2;
+    bool lc_d1_clean = false;  // this step's clears covered dfch's CLS blocks and the last block's fc-bias rows
     bool lc_active = false;  // the running step's forward ran trimmed (the backward follows it)
     bool lc_dirty = true;    // a backward (or nothing yet) wrote the shared gradient scratch since the last clear
     bool lc_pending = false; // the clears are in flight on s2 (EV_LC)
     bool last_cls_on() const { return last_cls && prec == VIT_BF16; }
+    // the bf16 weight gradient dW[OC,Cin] += dout^T . inp over all B*T rows (wgrad)
+    GemmArgs wgrad_args(const bf16_t* dout, int OC, const bf16_t* inp, int Cin, float* dW, int k_period) const {
+        GemmArgs w;
+        w.A = dout; w.lda = OC; w.a_kcontig = false;
+        w.B = inp; w.ldb = Cin; w.b_kcontig = false;
+        w.C = dW; w.ldc = Cin; w.M = OC; w.N = Cin; w.K = (int)BT; w.epi = EPI_F32_ATOMIC;
+        w.ws = gemm_ws; w.ws_bytes = gemm_ws_bytes;
+        // split-K fill: beside the micro-batch streams (concurrency on) the engine default (45 %: fewer
+        // splits, their half-filled rounds shared); alone on the GPU (concurrency off: the bench's
+        // per-kernel timing pass) 80 % of the slots
+        w.fill_pct = two_streams ? 0 : 80;
+        w.k_period = k_period;  // (bf16 engine: dout's rows off k_period are exact zeros, last_cls_bwd)
+        return w;
+    }
+    // layer l's fcproj dgrad of micro-batch mb into d1: full size (false), or (last_cls_bwd = 2, last block)
+    // gathered on the CLS rows when T >= 128, the full-size call would run on the 256x256 engine (not the
+    // ping-pong engine, whose partial rows are 96 tall), the dgrads read the transposed weights and the fc
+    // weight gradient of the step skips the K-steps without a CLS row (it then reads dfch in the CLS rows'
+    // 32-row blocks only).  Sets fcb_rows (the full-size call's partial rows per micro-batch).
+    bool lc_d1_gathered(int l, int mb, const bf16_t* dres3, GemmArgs& d1) {
+        const int Bm = B / nmb;
+        const long long R = (long long)Bm * T, r0 = mb * R;
+        LayerActs& a = la[l];
+        d1 = GemmArgs();
+        d1.A = dres3 + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C, 4 * C);
+        d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
+        d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
+        fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
+        d1.colsum_part = sg_rows(l, sg_fcb) + (long long)mb * fcb_rows * 4 * C;
+        if (!(last_cls_on() && lc_bwd >= 2 && l == L - 1 && T >= 128 && R >= 256 && dgrad_wt)) return false;
+        GemmArgs g = d1;
+        g.M = Bm; g.lda = (long long)T * C; g.ldc = (long long)T * 4 * C; g.ldaux = (long long)T * 4 * C;
+        g.rows_gathered = true; g.colsum_row_period = T;
+        if (!gemm_colsum_period_ok(g) || gemm_colsum_rows(g, false) != fcb_rows) return false;
+        if (!gemm_bf16_kskip(wgrad_args(dfch, 4 * C, a.ln2, C, G(P_FCW, l), T))) return false;
+        d1 = g;
+        return true;
+    }
     // dln_bf (the fc dgrad's output) and datty are scratch shared by all layers: after a backward they
     // hold layer 0's rows.  The last block's LayerNorm 2 backward and attention backward read every row
     // of them, and the trimmed fc / attproj dgrads write only the CLS rows, so the rest must be zero
@@ -1101,6 +1156,16 @@ struct Trainer {
         }
         VIT_HIP(hipMemsetAsync(dln_bf, 0, (size_t)BT * C * 2, cs));
         VIT_HIP(hipMemsetAsync(datty, 0, (size_t)BT * C * 2, cs));
+        // last_cls_bwd = 2: the gathered fcproj dgrad writes only the CLS rows of dfch and of the fc-bias
+        // partial rows.  The fc weight gradient reads dfch in the CLS rows' 32-row blocks, which hold layer
+        // 0's rows (nothing else reads a non-CLS row of dfch in the last block), and the fixed-order reduce
+        // reads every partial row
+        GemmArgs d1;
+        lc_d1_clean = lc_d1_gathered(L - 1, 0, dres_bf, d1);
+        if (lc_d1_clean) {
+            VIT_HIP(hipMemsetAsync(sg_rows(L - 1, sg_fcb), 0, (size_t)nmb * fcb_rows * 4 * C * sizeof(float), cs));
+            clear_cls_blocks_k<<<dim3(8, B), 256, 0, cs>>>(dfch, T, BT, 4 * C);
+        }
         if (cs != s) {
             VIT_HIP(hipEventRecord(bev[EV_LC], cs));
             lc_pending = true;
@@ -1304,16 +1369,8 @@ struct Trainer {
     // event `done` marks the end of its reads of dout / inp
     // dout_c / inp_c: column forms already written (rowcol_on(); dout_c's producer recorded `ready`)
     void wgrad(int cls, const bf16_t* dout, int OC, const bf16_t* inp, int Cin, float* dW, int ready,
-               int done, const QMat* dout_c = nullptr, const QMat* inp_c = nullptr) {
-        GemmArgs w;
-        w.A = dout; w.lda = OC; w.a_kcontig = false;
-        w.B = inp; w.ldb = Cin; w.b_kcontig = false;
-        w.C = dW; w.ldc = Cin; w.M = OC; w.N = Cin; w.K = (int)BT; w.epi = EPI_F32_ATOMIC;
-        w.ws = gemm_ws; w.ws_bytes = gemm_ws_bytes;
-        // split-K fill: beside the micro-batch streams (concurrency on) the engine default (45 %: fewer
-        // splits, their half-filled rounds shared); alone on the GPU (concurrency off: the bench's
-        // per-kernel timing pass) 80 % of the slots
-        w.fill_pct = two_streams ? 0 : 80;
+               int done, const QMat* dout_c = nullptr, const QMat* inp_c = nullptr, int k_period = 0) {
+        GemmArgs w = wgrad_args(dout, OC, inp, Cin, dW, k_period);
         hipStream_t st = two_streams ? s2 : s;
         if (two_streams) {
             for (int mb = 0; mb < nmb; mb++) {
@@ -1383,6 +1440,8 @@ struct Trainer {
         pre_side_wait();  // the arena clear and the transposed weights (side pre-work on s2)
         last_cls_wait();  // the per-step clears of dln_bf / datty (the micro-batch streams fork off s below)
         lc_dirty = true;
+        const bool d1_clean = lc_d1_clean;  // (this backward overwrites what the clears prepared)
+        lc_d1_clean = false;
         // the residual-gradient stream is "bf16 + lo8" (common.h: a bf16 plane, the GEMM operand,
         // plus a byte plane of its rounding residual; a 16-bit significand in 3 bytes): dres3 (the
         // layer output's gradient) in rbA/loA, dres2 in rbB/loB; each LayerNorm backward reads one
@@ -1407,13 +1466,16 @@ struct Trainer {
             const float* xl = l == 0 ? encoded : la[l - 1].res3;
             // last_cls: dres3 is zero off the CLS rows (head_backward), so dfch, dln2 and dres2 are too: the
             // fc and attproj input gradients run on the Bm CLS rows (row stride T, in place), and the rows
-            // they skip were cleared (last_cls_clear).  The weight gradients stay full size, and so do the
-            // fcproj dgrad and LayerNorm 2 backward, whose partial rows make fc_b, ln2_w, ln2_b and
-            // attproj_b: summed over the same rows in the same order, they keep their bits
+            // they skip were cleared (last_cls_clear).  The weight gradients, the fcproj dgrad and LayerNorm 2
+            // backward (whose partial rows make fc_b, ln2_w, ln2_b and attproj_b) stay full size, or
+            // (last_cls_bwd, below) take forms that add the same values in the same order: they keep their bits
             const bool lc = lc_active && l == L - 1;
             const int Mr = lc ? Bm : (int)R;
             const long long rs = lc ? T : 1;
             const bool lcg = lc && R >= 256;  // (as in forward_bf16: the engine of the full-size form)
+            // last_cls_bwd: the three weight gradients' dout (dres3, dfch, dres2) is exact zeros off the CLS
+            // rows, so their split-K engine walks only the K-steps that hold a CLS row (GemmArgs::k_period)
+            const int kper = lc && lc_bwd >= 1 ? T : 0;
             // rowcol: the weight gradients whose dout column form the dgrads' quantize step writes
             // are issued after those dgrads (s2 waits on the event recorded after the quantize)
             const bool rc = rowcol_on();
@@ -1424,16 +1486,21 @@ struct Trainer {
             // fcproj: dfch = (dres3 . fcprojw) * gelu'(fch) (stored as fchd);  fcprojw += dres3^T . fchg
             const bool ec = epicol_on();
             QMat c_fchg = ec ? fchgc_of(l) : QMat{};
-            if (!rc) wgrad(TC_FCPROJ_WGRAD, rbA, C, a.fchg, 4 * C, G(P_FCPROJW, l), EV_RESA, EV_W1);
+            if (!rc) wgrad(TC_FCPROJ_WGRAD, rbA, C, a.fchg, 4 * C, G(P_FCPROJW, l), EV_RESA, EV_W1, nullptr, nullptr, kper);
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 after_wgrad(EV_W2, ms[mb]);  // the previous layer's fc wgrad has read dfch
-                GemmArgs d1;
-                d1.A = rbA + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C, 4 * C);
-                d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
-                d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
-                fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
-                d1.colsum_part = sg_rows(l, sg_fcb) + (long long)mb * fcb_rows * 4 * C;
+                GemmArgs d1, d1g;
+                // (last_cls_bwd = 2 in the last block: on the CLS rows, where this step's clears covered it)
+                if (lc && d1_clean && !ec && lc_d1_gathered(l, mb, rbA, d1g)) {
+                    d1 = d1g;
+                } else {
+                    d1.A = rbA + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C, 4 * C);
+                    d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
+                    d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
+                    fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
+                    d1.colsum_part = sg_rows(l, sg_fcb) + (long long)mb * fcb_rows * 4 * C;
+                }
                 if (ec) {  // dfch only as its row (mx_out) and column MX forms
                     d1.C = nullptr;
                     d1.mxc_q = dfchc.q; d1.mxc_s = dfchc.s; d1.mxc_ld = kp_tok; d1.mxc_off = r0;
@@ -1446,7 +1513,7 @@ struct Trainer {
                           ec ? &c_fchg : nullptr);
             // fc: dln2 = dfch . fcw;  fcw += dfch^T . ln2
             wgrad(TC_FC_WGRAD, dfch, 4 * C, a.ln2, C, G(P_FCW, l), EV_DFCH, EV_W2, ec ? &dfchc : nullptr,
-                  rc ? &c_ln2 : nullptr);
+                  rc ? &c_ln2 : nullptr, kper);
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d2;
@@ -1474,7 +1541,7 @@ struct Trainer {
                 tend();
             }
             // attproj
-            if (!rc) wgrad(TC_PROJ_WGRAD, rbB, C, a.atty, C, G(P_ATTPROJW, l), EV_RESB, EV_W3);
+            if (!rc) wgrad(TC_PROJ_WGRAD, rbB, C, a.atty, C, G(P_ATTPROJW, l), EV_RESB, EV_W3, nullptr, nullptr, kper);
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d3;
@@ -2518,11 +2585,15 @@ int vit_trainer_set_concurrency(vit_trainer_t* h, int on) {
     for (int k = 0; k < vit::Trainer::MAXMB; k++) if (t.ms[k]) VIT_HIP(hipStreamSynchronize(t.ms[k]));
     t.two_streams = on != 0;
     t.nmb = t.pick_nmb(t.mb_want);
+    t.lc_dirty = true;
+    t.lc_d1_clean = false;
     return vit::has_error();
 }
 int vit_trainer_set_option(vit_trainer_t* h, const char* name, int value) {
     auto& t = h->t;
     VIT_HIP(hipDeviceSynchronize());
+    t.lc_dirty = true;  // (last_cls: the next forward redoes its clears for the new settings)
+    t.lc_d1_clean = false;
     const std::string n = name ? name : "";
     if (n == "microbatch") {
         t.mb_want = value;
@@ -2548,6 +2619,8 @@ int vit_trainer_set_option(vit_trainer_t* h, const char* name, int value) {
         t.clip_overlap = value < 0 ? -1 : value != 0;
     } else if (n == "last_cls") {  // bf16: the last block's row-wise ops after attention on the CLS rows only (default 1)
         t.last_cls = value != 0;
+    } else if (n == "last_cls_bwd") {  // bf16, with last_cls: the last block's weight gradients on the CLS K-steps (1) and its fcproj dgrad on the CLS rows (2, default)
+        t.lc_bwd = value < 0 ? 0 : value;
     } else if (n == "dp_probe") {
         if (value && !t.dp_snap) {  // allocated once, kept until destroy
             t.dp_snap = t.alloc<float>(t.arena_elems);
