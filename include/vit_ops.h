@@ -45,7 +45,8 @@ int vit_memcpy_d2h(void* dst, const void* src, size_t bytes);
 int vit_memcpy_d2d(void* dst, const void* src, size_t bytes);
 int vit_memset(void* dst, int value, size_t bytes);
 /* launch counters: how many launches of each kernel family ran since the last reset (process-wide,
- * every thread and stream).  GEMM families are indexed base + epilogue (epi < 16, gemm.h Epi). */
+ * every thread and stream).  GEMM families are indexed base + epilogue (epi < 16, gemm.h Epi; 12 = the
+ * row-scaled residual epilogue of gemm_bf16_fused_rowscale). */
 enum {
     VIT_HIT_GEMM_128 = 0,            /* bf16 128x128 register-staged (small / ragged shapes) */
     VIT_HIT_GEMM_256x256 = 16,       /* bf16 256x256 LDS-DMA engine, one workgroup per CU */
@@ -216,6 +217,18 @@ void gemm_bf16_fused_rows(void* C, void* C2, long long ldc, const void* aux, lon
                           const uint16_t* A, long long lda, int a_kcontig, const uint16_t* B,
                           long long ldb, int b_kcontig, const float* bias, float* colsum_out, int M,
                           int N, int K, int epi, int rows_gathered, int colsum_row_period);
+/* gemm_bf16_fused_rows with epi 12, the row-scaled residual epilogue of stochastic depth
+ * (vit_trainer_set_drop_path): C_f32[m][n] = aux_f32[m*ldaux + n] + fl32(row_scale[m * ld_row_scale] *
+ * (acc + bias[n])), the product rounded to fp32 on its own (no FMA), so row_scale == 1 gives the bits of
+ * epi 5 and row_scale == 0 gives C == aux.  row_scale: fp32 device pointer; a row-gathered call passes the
+ * dense per-row table with ld_row_scale = the rows' stride.  colsum_out must be NULL and
+ * colsum_row_period 0 (the epilogue sums no columns); C2 is unused.  Runs on the 128x128 engine and both
+ * 256x256 forms; the ping-pong engine of variant 11 declines it (the call then takes the default engine). */
+void gemm_bf16_fused_rowscale(void* C, void* C2, long long ldc, const void* aux, long long ldaux,
+                              const uint16_t* A, long long lda, int a_kcontig, const uint16_t* B,
+                              long long ldb, int b_kcontig, const float* bias, float* colsum_out, int M,
+                              int N, int K, int epi, int rows_gathered, int colsum_row_period,
+                              const float* row_scale, long long ld_row_scale);
 /* ------------------------------------------------------------------ fp8 (MXFP8) GEMM path
  * OCP fp8 e4m3 operands with one E8M0 scale per 32 consecutive k-elements of a row (OCP MX block
  * scaling) on v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulate: the fp8 mode's forward and

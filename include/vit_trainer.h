@@ -138,6 +138,40 @@ int vit_trainer_set_param_groups(vit_trainer_t* t, const float* lr_mul, const fl
 /* the multipliers in force (ones when off; either pointer may be NULL); *on (nullable) = 1 if
  * groups are on */
 int vit_trainer_get_param_groups(vit_trainer_t* t, float* lr_mul, float* wd_mul, int* on);
+/* ---- stochastic depth / drop path: a table s[l][br][b] of non-negative finite scales, l the
+ *      layer, br 0 = the attention branch and 1 = the MLP branch, b the image ([num_layers][2][batch]
+ *      floats).  With y the branch's output (its bias included), for every row r of image b:
+ *        forward:   x_out[r] = x_in[r] + fl32(s * y[r])       (the product rounded to fp32 on its own, no FMA);
+ *        backward:  the pass-through gradient is unchanged; the branch's upstream gradient is
+ *                   dy[r] = fl32(s * dout[r]), taken from the fp32 value (in bf16 mode that product, rounded
+ *                   to bf16, is the operand of the branch's input- and weight-gradient GEMMs); the branch's
+ *                   last bias gradient (attproj_b, fcproj_b) is the column sum of those fp32 products.
+ *      s = 0 drops the branch for an image, s = 1 / (1 - p) keeps it at the usual rescale; 1.0f * x == x, so an
+ *      all-ones table gives the bits of a step without one.  A trainer that never sets a table issues
+ *      exactly the launches it did before.  VIT_FP32 and VIT_BF16 modes. ---- */
+/* one-shot, like vit_trainer_set_augment_plan: the table applies to the next vit_trainer_forward /
+ * vit_trainer_train_step of a batch that has labels and to that forward's backward, and is cleared by it (a
+ * stale mask never repeats).  vit_trainer_eval and forwards of a batch without labels never drop and
+ * leave a pending table pending.  NULL clears a pending table.  An entry that is not finite and >= 0:
+ * non-zero + vit_last_error, the previous state stays.  VIT_FP8 mode: an error ("not supported in fp8
+ * mode").  Returns once the host array has been read; the device buffers (the per-row table and, in bf16
+ * mode, two [B*T, C] bf16 planes) are allocated by the first call and counted in
+ * vit_trainer_device_bytes.  Not written to checkpoints. */
+int vit_trainer_set_drop_path(vit_trainer_t* t, const float* host_scales);
+/* the table the last training forward used into out ([num_layers][2][batch], nullable); *used (nullable)
+ * = 0 if that forward ran without one (out is then left as it is) */
+int vit_trainer_get_drop_path(vit_trainer_t* t, float* out, int* used);
+/* host-only draw of such a table (no GPU call), out [num_layers][2][batch]:
+ *   p_l = linear ? (float)((double)rate * l / (num_layers - 1)) : rate   (rate for num_layers == 1; timm's
+ *         linspace(0, rate, depth));
+ *   w   = the splitmix64 counter stream of s = seed ^ splitmix64(0x64726f7070617468, key) at position
+ *         (2 l + br) * batch + b (the generator of the loaders' shuffle and vit_randaugment_draw);
+ *   u   = (w >> 40) * 2^-24; the branch is kept iff u >= p_l;
+ *   out = kept ? 1.0f / (1.0f - p_l) : 0.0f   (fp32 IEEE division).
+ * The caller chooses key, e.g. step * world + rank, so that ranks draw different masks.  rate outside
+ * [0, 1) (or a bad size): non-zero + vit_last_error. */
+int vit_drop_path_draw(unsigned long long seed, long long key, int num_layers, int batch, float rate,
+                       int linear, float* out);
 /* canonical host copies of m, v (either may be NULL) and the step count; synchronous */
 int vit_trainer_get_adamw_state(vit_trainer_t* t, float* m, float* v, int* step);
 /* eval: forward of the current batch, then top-1 per image on the device.

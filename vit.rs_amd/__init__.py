@@ -23,6 +23,7 @@ from . import data  # noqa: E402  (configs, canonical layout, seeded synthetic i
 from . import mix  # noqa: E402  (mixup / cutmix draws and their numpy statement)
 from . import groups  # noqa: E402  (parameter-group tables: no_decay, layer_decay)
 from . import augment  # noqa: E402  (RandAugment: the policy draw and its numpy statement)
+from . import droppath  # noqa: E402  (stochastic depth: the per-step table draw)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
@@ -110,6 +111,7 @@ _SIGS = {
     "gemm_bf16_kperiod": (None, [P, LL, P, LL, I, P, LL, I, I, I, I, I, I, I]),
     "gemm_bf16_fused": (None, [P, P, LL, P, LL, P, LL, I, P, LL, I, P, P, I, I, I, I]),
     "gemm_bf16_fused_rows": (None, [P, P, LL, P, LL, P, LL, I, P, LL, I, P, P, I, I, I, I, I, I]),
+    "gemm_bf16_fused_rowscale": (None, [P, P, LL, P, LL, P, LL, I, P, LL, I, P, P, I, I, I, I, I, I, P, LL]),
     "mx_scale_size": (LL, [LL, I]),
     "quantize_mx_bf16_ex": (None, [P, P, P, LL, I, LL, LL]),
     "quantize_mx_f32_ex": (None, [P, P, P, LL, I, LL, LL]),
@@ -156,6 +158,9 @@ _SIGS = {
     "vit_trainer_set_param_groups": (I, [P, P, P]),
     "vit_trainer_get_param_groups": (I, [P, P, P, ctypes.POINTER(I)]),
     "vit_trainer_eval": (I, [P, P, ctypes.POINTER(I)]),
+    "vit_trainer_set_drop_path": (I, [P, P]),
+    "vit_trainer_get_drop_path": (I, [P, P, ctypes.POINTER(I)]),
+    "vit_drop_path_draw": (I, [ctypes.c_ulonglong, LL, I, I, F, I, P]),
     # checkpoints (include/vit_checkpoint.h; host-only)
     "vit_config_num_params": (LL, [ctypes.POINTER(VitConfigC)]),
     "vit_checkpoint_read_info": (I, [ctypes.c_char_p, P]),
@@ -733,6 +738,26 @@ class ViT:
         self._ok(lib().vit_trainer_get_param_groups(self.h, lr.ctypes.data_as(P), wd.ctypes.data_as(P),
                                                     ctypes.byref(on)), "get_param_groups")
         return lr, wd, bool(on.value)
+
+    def set_drop_path(self, scales):
+        """One-shot stochastic-depth table [L, 2, B] (layer; 0 attention / 1 MLP branch; image) of
+        non-negative finite scales for the next training forward and its backward only; None clears a
+        pending table (vit_trainer_set_drop_path; see droppath.draw / droppath.DropPath)."""
+        if scales is None:
+            self._ok(lib().vit_trainer_set_drop_path(self.h, None), "set_drop_path")
+            return
+        a = np.ascontiguousarray(scales, dtype=np.float32)
+        assert a.shape == (self.cfg.num_layers, 2, self.B), a.shape
+        self._ok(lib().vit_trainer_set_drop_path(self.h, a.ctypes.data_as(P)), "set_drop_path")
+
+    def drop_path(self):
+        """The table [L, 2, B] the last training forward used, or None if it ran without one
+        (vit_trainer_get_drop_path)."""
+        out = np.empty((self.cfg.num_layers, 2, self.B), np.float32)
+        used = ctypes.c_int()
+        self._ok(lib().vit_trainer_get_drop_path(self.h, out.ctypes.data_as(P), ctypes.byref(used)),
+                 "get_drop_path")
+        return out if used.value else None
 
     def adamw_state(self):
         """(m, v, t) in canonical order."""

@@ -29,7 +29,14 @@ enum Epi {
     // instances of their own, so the dense epilogues keep their code and registers
     EPI_BF16_DGELU_ROWS = 10,
     EPI_BF16_MUL_ROWS = 11,
+    // stochastic depth: EPI_F32_RESID with the branch output scaled per row,
+    // C_f32 = aux_f32[m*ldaux + n] + fl32(row_scale[m*ld_row_scale] * (acc + bias)), the product rounded
+    // to fp32 on its own (no FMA).  An instance of its own: EPI_F32_RESID keeps its code
+    EPI_F32_RESID_RS = 12,
 };
+// epilogues that read an fp32 aux operand the shape of C (the residual stream, or C itself)
+constexpr bool epi_aux32(int e) { return e == EPI_F32_RESID || e == EPI_F32_ACC || e == EPI_F32_RESID_RS; }
+constexpr bool epi_resid(int e) { return e == EPI_F32_RESID || e == EPI_F32_RESID_RS; }  // (aux32 from aux, not C)
 // epilogues that read a bf16 aux operand / that may sum the output's columns (colsum_out)
 constexpr bool epi_rows(int e) { return e == EPI_BF16_DGELU_ROWS || e == EPI_BF16_MUL_ROWS; }
 constexpr bool epi_aux16(int e) { return e == EPI_BF16_DGELU || e == EPI_BF16_MUL || epi_rows(e); }
@@ -52,6 +59,10 @@ struct GemmArgs {
     const void* aux = nullptr;
     long long ldaux = 0;
     const float* bias = nullptr;
+    // EPI_F32_RESID_RS: the scale of output row m is row_scale[m * ld_row_scale] (fp32; a row-gathered
+    // call passes the dense table with the rows' stride)
+    const float* row_scale = nullptr;
+    long long ld_row_scale = 1;
     float* dbias = nullptr;  // bf16 wgrad with an M-contig A: dbias[m] += sum_k A(m,k) (fused colsum)
     // EPI_BF16_DGELU / EPI_BF16_MUL column sums of the output, deterministic: the epilogue stores
     // partial rows colsum_part[gemm_colsum_rows(a)][N] (row r = output rows 128r..128r+127, 96r.. on the

@@ -1179,6 +1179,8 @@ GemmParams make_gemm_params(const GemmArgs& a, int kchunk) {
     p.tiles = 1;
     p.k_period = 0;  // (the 256x128 launcher sets it)
     p.colsum_row_period = 0;  // (gemm_bf16 sets it on the 256x256 engines)
+    p.row_scale = a.row_scale;
+    p.ld_row_scale = a.ld_row_scale;
     return p;
 }
 
@@ -1285,6 +1287,7 @@ static void launch_bf16(const GemmArgs& a, const GemmParams& p, dim3 grid, hipSt
         VIT_CASE(EPI_BF16_DGELU)
         VIT_CASE(EPI_BF16_GELU_D)
         VIT_CASE(EPI_BF16_MUL)
+        VIT_CASE(EPI_F32_RESID_RS)
 #undef VIT_CASE
         default: set_error("gemm_bf16: unsupported epilogue %d", a.epi); return;
     }
@@ -1313,6 +1316,7 @@ static void launch_g2(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStre
                 VIT_CASE(EPI_BF16_MUL)
                 VIT_CASE(EPI_BF16_DGELU_ROWS)
                 VIT_CASE(EPI_BF16_MUL_ROWS)
+                VIT_CASE(EPI_F32_RESID_RS)
 #undef VIT_CASE
                 default: break;
             }
@@ -1339,6 +1343,7 @@ static void launch_g2(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStre
         VIT_CASE(EPI_F32_SLAB)
         VIT_CASE(EPI_BF16_GELU_D)
         VIT_CASE(EPI_BF16_MUL)
+        VIT_CASE(EPI_F32_RESID_RS)
 #undef VIT_CASE
         default: set_error("gemm_bf16: unsupported epilogue %d", a.epi); return;
     }
@@ -1454,6 +1459,10 @@ void gemm_bf16(const GemmArgs& a, hipStream_t s) {
     }
     if (epi_rows(a.epi)) {
         set_error("gemm_bf16: epilogue %d is internal (colsum_row_period)", a.epi);
+        return;
+    }
+    if (a.epi == EPI_F32_RESID_RS && !(a.row_scale && a.aux && a.ld_row_scale >= 0)) {
+        set_error("gemm_bf16: the row-scaled residual epilogue needs aux and row_scale (ld_row_scale >= 0)");
         return;
     }
     if (a.colsum_row_period != 0 && !gemm_colsum_period_ok(a)) {

@@ -37,6 +37,8 @@ struct GemmParams {
     uint8_t* mxc_s;
     long long mxc_ld;
     int mxc_off, mxc_rg;
+    const float* row_scale;  // EPI_F32_RESID_RS (GemmArgs::row_scale / ld_row_scale)
+    long long ld_row_scale;
 };
 
 // E8M0 scale byte of an MX block: X + 127 with X = ceil(log2(amax / 448)) (no element overflows
@@ -203,6 +205,13 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, int m, int n, f32x
                                                           (long long)m * p.ldaux + n);
         *reinterpret_cast<float4*>((float*)p.C + off) =
             make_float4(v[0] + r.x, v[1] + r.y, v[2] + r.z, v[3] + r.w);
+    } else if constexpr (EPI == EPI_F32_RESID_RS) {
+#pragma clang fp contract(off)  // the scaled branch output is rounded before the residual add
+        const float4 r = *reinterpret_cast<const float4*>((const float*)p.aux +
+                                                          (long long)m * p.ldaux + n);
+        const float sc = p.row_scale[(long long)m * p.ld_row_scale];
+        const float y0 = sc * v[0], y1 = sc * v[1], y2 = sc * v[2], y3 = sc * v[3];
+        *reinterpret_cast<float4*>((float*)p.C + off) = make_float4(r.x + y0, r.y + y1, r.z + y2, r.w + y3);
     } else if constexpr (EPI == EPI_F32_SLAB) {
         float* slab = (float*)p.C + (long long)split_index(p.tiles) * p.M * p.ldc;
         *reinterpret_cast<float4*>(slab + off) = make_float4(v[0], v[1], v[2], v[3]);
@@ -284,6 +293,21 @@ __device__ __forceinline__ void epilogue8(const GemmParams& p, int m, int n, flo
         v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w;
         v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
         st_f32((float*)p.C + off);
+    } else if constexpr (EPI == EPI_F32_RESID_RS) {
+        const float* r = (const float*)p.aux + (long long)m * p.ldaux + n;
+        const float4 r0 = reinterpret_cast<const float4*>(r)[0];
+        const float4 r1 = reinterpret_cast<const float4*>(r)[1];
+        const float ra[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+        const float sc = p.row_scale[(long long)m * p.ld_row_scale];
+        {  // the scaled branch output is rounded before the residual add (no FMA contraction)
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float y = sc * v[j];
+            v[j] = ra[j] + y;
+        }
+        }
+        st_f32((float*)p.C + off);
     } else if constexpr (EPI == EPI_BF16_GELU_D) {
         float gv[8], dv[8];
 #pragma unroll
@@ -354,7 +378,7 @@ typedef unsigned int epi_u32x4v __attribute__((ext_vector_type(4)));
 template <int EPI>
 struct EpiAux {
     static constexpr bool AUX16 = epi_aux16(EPI);
-    static constexpr bool AUX32 = EPI == EPI_F32_RESID || EPI == EPI_F32_ACC;
+    static constexpr bool AUX32 = epi_aux32(EPI);
     static constexpr int N = AUX16 ? 8 : (AUX32 ? 16 : 0);
     epi_u32x4v ax[N > 0 ? N : 1];
     __device__ __forceinline__ void load(const GemmParams& p, int rr, int mrow, int n) {
@@ -363,8 +387,8 @@ struct EpiAux {
             for (int it = 0; it < 8; it++)
                 ax[it] = epi_ld16(p, (const bf16_t*)p.aux + (long long)(mrow + it * 8 + rr) * p.ldaux + n);
         } else if constexpr (AUX32) {
-            const float* src = EPI == EPI_F32_RESID ? (const float*)p.aux : (const float*)p.C;
-            const long long ld = EPI == EPI_F32_RESID ? p.ldaux : p.ldc;
+            const float* src = epi_resid(EPI) ? (const float*)p.aux : (const float*)p.C;
+            const long long ld = epi_resid(EPI) ? p.ldaux : p.ldc;
 #pragma unroll
             for (int it = 0; it < 8; it++) {
                 const float* q = src + (long long)(mrow + it * 8 + rr) * ld + n;
@@ -393,10 +417,16 @@ __device__ __forceinline__ void staged_pass_interior(const GemmParams& p, const 
         }
     }
     constexpr bool AUX16 = epi_aux16(EPI);
-    constexpr bool AUX32 = EPI == EPI_F32_RESID || EPI == EPI_F32_ACC;
+    constexpr bool AUX32 = epi_aux32(EPI);
     EpiAux<EPI> own;
     if (!pre) own.load(p, rr, mrow, n);
     const u32x4* ax = pre ? pre->ax : own.ax;
+    // EPI_F32_RESID_RS: the pass's row scales (rows mrow + 8 it + rr), loaded with the aux rows
+    [[maybe_unused]] float rsc[8];
+    if constexpr (EPI == EPI_F32_RESID_RS) {
+#pragma unroll
+        for (int it = 0; it < 8; it++) rsc[it] = p.row_scale[(long long)(mrow + it * 8 + rr) * p.ld_row_scale];
+    }
     float* slab = nullptr;
     if constexpr (EPI == EPI_F32_SLAB) slab = (float*)p.C + (long long)split_index(p.tiles) * p.M * p.ldc;
 #pragma unroll
@@ -420,6 +450,17 @@ __device__ __forceinline__ void staged_pass_interior(const GemmParams& p, const 
             st_f32((float*)p.C + off);
         } else if constexpr (EPI == EPI_F32_SLAB) {
             st_f32(slab + off);
+        } else if constexpr (EPI == EPI_F32_RESID_RS) {
+            {  // the scaled branch output is rounded before the residual add (no FMA contraction)
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float y0 = rsc[it] * v[j], y1 = rsc[it] * v[4 + j];
+                v[j] = __uint_as_float(ax[2 * it][j]) + y0;
+                v[4 + j] = __uint_as_float(ax[2 * it + 1][j]) + y1;
+            }
+            }
+            st_f32((float*)p.C + off);
         } else if constexpr (AUX32) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -640,7 +681,7 @@ __device__ __forceinline__ int sq_off(int r, int col) {
 template <int EPI>
 struct EpiAuxQ {  // aux operand rows of one interior 32-row pass (rows mrow + 8 it + rr, it < 4)
     static constexpr bool AUX16 = epi_aux16(EPI);
-    static constexpr bool AUX32 = EPI == EPI_F32_RESID || EPI == EPI_F32_ACC;
+    static constexpr bool AUX32 = epi_aux32(EPI);
     static constexpr int N = AUX16 ? 4 : (AUX32 ? 8 : 0);
     epi_u32x4v ax[N > 0 ? N : 1];
     __device__ __forceinline__ void load(const GemmParams& p, int rr, int mrow, int n) {
@@ -649,8 +690,8 @@ struct EpiAuxQ {  // aux operand rows of one interior 32-row pass (rows mrow + 8
             for (int it = 0; it < 4; it++)
                 ax[it] = epi_ld16(p, (const bf16_t*)p.aux + (long long)(mrow + it * 8 + rr) * p.ldaux + n);
         } else if constexpr (AUX32) {
-            const float* src = EPI == EPI_F32_RESID ? (const float*)p.aux : (const float*)p.C;
-            const long long ld = EPI == EPI_F32_RESID ? p.ldaux : p.ldc;
+            const float* src = epi_resid(EPI) ? (const float*)p.aux : (const float*)p.C;
+            const long long ld = epi_resid(EPI) ? p.ldaux : p.ldc;
 #pragma unroll
             for (int it = 0; it < 4; it++) {
                 const float* q = src + (long long)(mrow + it * 8 + rr) * ld + n;
@@ -706,8 +747,13 @@ __device__ __forceinline__ void staged_pass_interior_q(const GemmParams& p, floa
                                                        const EpiAuxQ<EPI>& aux) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     constexpr bool AUX16 = epi_aux16(EPI);
-    constexpr bool AUX32 = EPI == EPI_F32_RESID || EPI == EPI_F32_ACC;
+    constexpr bool AUX32 = epi_aux32(EPI);
     const int cc_lane = cc >> 3;
+    [[maybe_unused]] float rsc[4];  // EPI_F32_RESID_RS: the pass's row scales (rows mrow + 8 it + rr)
+    if constexpr (EPI == EPI_F32_RESID_RS) {
+#pragma unroll
+        for (int it = 0; it < 4; it++) rsc[it] = p.row_scale[(long long)(mrow + it * 8 + rr) * p.ld_row_scale];
+    }
 #pragma unroll
     for (int it = 0; it < 4; it++) {
         const int r = it * 8 + rr;
@@ -726,6 +772,17 @@ __device__ __forceinline__ void staged_pass_interior_q(const GemmParams& p, floa
             epi_st16(p, q + 4, u32x4{__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])});
         };
         if constexpr (EPI == EPI_F32_STORE) {
+            st_f32((float*)p.C + off);
+        } else if constexpr (EPI == EPI_F32_RESID_RS) {
+            {  // the scaled branch output is rounded before the residual add (no FMA contraction)
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float y0 = rsc[it] * v[j], y1 = rsc[it] * v[4 + j];
+                v[j] = __uint_as_float(aux.ax[2 * it][j]) + y0;
+                v[4 + j] = __uint_as_float(aux.ax[2 * it + 1][j]) + y1;
+            }
+            }
             st_f32((float*)p.C + off);
         } else if constexpr (AUX32) {
 #pragma unroll

@@ -532,7 +532,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_pp(GemmParams p) {
 }  // namespace g6
 
 // the shapes the ping-pong engine takes: K-contiguous A and B, no split-K, N % 256 == 0, K % 64 == 0
-// with >= 8 K-steps, M >= 192, 32-bit tile-relative offsets, no fused MX output
+// with >= 8 K-steps, M >= 192, 32-bit tile-relative offsets, no fused MX output, and an epilogue this
+// engine implements (not EPI_F32_RESID_RS, the row-scaled residual: that call takes the default engine)
 bool gemm_pp_shape(const GemmArgs& a) {
     if (!a.a_kcontig || !a.b_kcontig || a.mx_q || a.mxc_q) return false;
     if (a.N % g6::BN || a.K % 64 || a.K / g6::BK < 8 || a.M < g6::BM) return false;

@@ -210,6 +210,11 @@ __global__ __launch_bounds__(256) void ln_fwd_k(TO* __restrict__ out, float* __r
 // are summed across the 4 waves in a fixed order and leave the block as its partial row
 // part[blockIdx.x][2C or 3C] (dw | db | dsum), summed in a fixed order by rows_reduce_add — by the
 // launcher, or by the trainer across micro-batches: deterministic.  TD: dout type (fp32 or bf16).
+//   DP (ST only; stochastic depth): out is also the upstream gradient of a residual branch
+//               whose forward scaled row r by rscale[r]: the kernel also writes the plane
+//               hi_scaled = bf16(fl32(rscale[r] * out)) (the operand of that branch's dgrad / wgrad GEMMs)
+//               and dsum sums the fp32 products instead of out (the branch's last bias gradient); hi_out /
+//               lo_out, the pass-through gradient, are written as without it.  Instantiations of their own.
 struct LnbIo {
     float* dinp;            // ST = false: accumulated in place
     bf16_t* hi_out;         // ST = true
@@ -217,6 +222,8 @@ struct LnbIo {
     const bf16_t* hi_in;
     const uint8_t* lo_in;
     float *dweight, *dbias, *dsum, *part;
+    const float* rscale;    // DP
+    bf16_t* hi_scaled;
 };
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16_t v) { return bf2f(v); }
@@ -229,7 +236,7 @@ __device__ __forceinline__ void lnb_flush(const LnbIo& io, const float* sm, int 
     }
 }
 // any C (the vectorised kernel below needs C % 256 == 0)
-template <typename TD, bool ST>
+template <typename TD, bool ST, bool DP = false>
 __global__ __launch_bounds__(256) void ln_bwd_k(LnbIo io, const TD* __restrict__ dout,
                                                 const float* __restrict__ inp,
                                                 const float* __restrict__ weight,
@@ -246,6 +253,8 @@ __global__ __launch_bounds__(256) void ln_bwd_k(LnbIo io, const TD* __restrict__
         const TD* dy = dout + row * C;
         const float* x = inp + row * C;
         const float mu = mean[row], rs = rstd[row];
+        [[maybe_unused]] float sc = 1.f;
+        if constexpr (DP) sc = io.rscale[row];
         float a = 0.f, bsum = 0.f;
         for (int i = lane; i < C; i += 64) {
             const float d = to_f32(dy[i]);
@@ -272,7 +281,14 @@ __global__ __launch_bounds__(256) void ln_bwd_k(LnbIo io, const TD* __restrict__
                 const bf16_t h = f2bf(t);
                 io.hi_out[o] = h;
                 io.lo_out[o] = (uint8_t)lo8_encode(t, bf2f(h));
-                ps[i] += t;
+                if constexpr (DP) {
+#pragma clang fp contract(off)  // the product is rounded before the plane and the column sum
+                    const float u = sc * t;
+                    io.hi_scaled[o] = f2bf(u);
+                    ps[i] += u;
+                } else {
+                    ps[i] += t;
+                }
             } else {
                 io.dinp[o] += dval;
             }
@@ -325,7 +341,7 @@ __device__ __forceinline__ float4 ld4(const bf16_t* p, int k) {
 // C % 256 == 0: one wave per row, NV float4 per lane in registers, the next row's loads in flight
 // while this row reduces and stores (every load unconditional — the last row re-fetches itself — so
 // the compiler never drains the prefetch with a vmcnt(0))
-template <int NV, typename TD, bool ST>
+template <int NV, typename TD, bool ST, bool DP = false>
 __global__ __launch_bounds__(256) void ln_bwd_vec_k(LnbIo io, const TD* __restrict__ dout,
                                                     const float* inp,  // not restrict: keeps its prefetch above the row's stores
                                                     const float* __restrict__ weight,
@@ -349,6 +365,7 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_k(LnbIo io, const TD* __restri
     float4 pdy[NV], px[NV], pri[NV];
     uint32_t plo[NV];
     float pmu = 0.f, prs = 0.f;
+    [[maybe_unused]] float psc = 1.f;  // DP: the row's scale
     auto fetch = [&](long long r) {
         const TD* dyr = dout + r * C;
         const float4* x4 = reinterpret_cast<const float4*>(inp + r * C);
@@ -365,6 +382,7 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_k(LnbIo io, const TD* __restri
         }
         pmu = mean[r];
         prs = rstd[r];
+        if constexpr (DP) psc = io.rscale[r];
     };
     long long row = blockIdx.x * 4LL + wave;
     if (row < rows) fetch(row);
@@ -382,6 +400,7 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_k(LnbIo io, const TD* __restri
             }
         }
         const float mu = pmu, rs = prs;
+        [[maybe_unused]] const float sc = psc;
         fetch(row + nwaves < rows ? row + nwaves : row);
         // keep the prefetch at the top: the scheduler otherwise sinks it to the end of the row to
         // reuse this row's registers, and the next iteration waits a full HBM round trip
@@ -403,7 +422,15 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_k(LnbIo io, const TD* __restri
             const float4 t = make_float4(ri[j].x + dv.x, ri[j].y + dv.y, ri[j].z + dv.z, ri[j].w + dv.w);
             if constexpr (ST) {
                 float4 u = ps[k];
-                u.x += t.x; u.y += t.y; u.z += t.z; u.w += t.w;
+                if constexpr (DP) {
+#pragma clang fp contract(off)  // the products are rounded before the plane and the column sums
+                    const float4 y = make_float4(sc * t.x, sc * t.y, sc * t.z, sc * t.w);
+                    u.x += y.x; u.y += y.y; u.z += y.z; u.w += y.w;
+                    reinterpret_cast<uint2*>(io.hi_scaled + row * C)[k] =
+                        make_uint2(pack_bf16x2(y.x, y.y), pack_bf16x2(y.z, y.w));
+                } else {
+                    u.x += t.x; u.y += t.y; u.z += t.z; u.w += t.w;
+                }
                 ps[k] = u;
                 const uint2 h = make_uint2(pack_bf16x2(t.x, t.y), pack_bf16x2(t.z, t.w));
                 reinterpret_cast<uint2*>(io.hi_out + row * C)[k] = h;
@@ -815,7 +842,7 @@ void ln_forward_bf16(bf16_t* out, float* mean, float* rstd, const float* inp, co
     ln_forward_any<bf16_t>(out, mean, rstd, inp, w, b, rows, C, s, row_stride);
 }
 int ln_bwd_blocks(long long rows);
-template <typename TD, bool ST>
+template <typename TD, bool ST, bool DP = false>
 static void ln_backward_any(LnbIo io, const TD* dout, const float* inp, const float* w,
                             const float* mean, const float* rstd, long long rows, int C, hipStream_t s,
                             float* ws = nullptr) {
@@ -830,19 +857,20 @@ static void ln_backward_any(LnbIo io, const TD* dout, const float* inp, const fl
     }
     const bool vec = C % 256 == 0 && C <= 2048 &&
                      (((uintptr_t)io.dinp | (uintptr_t)dout | (uintptr_t)inp | (uintptr_t)w |
-                       (uintptr_t)io.hi_in | (uintptr_t)io.hi_out | (uintptr_t)io.lo_in | (uintptr_t)io.lo_out) & 15) == 0;
+                       (uintptr_t)io.hi_in | (uintptr_t)io.hi_out | (uintptr_t)io.lo_in | (uintptr_t)io.lo_out |
+                       (uintptr_t)io.hi_scaled) & 15) == 0;
     const int grid = ln_bwd_blocks(rows);
     const size_t lds = 12 * (size_t)C * sizeof(float);
     if (lds > 160 * 1024) { set_error("layernorm_backward: C=%d exceeds the LDS column partials", C); return; }
     if (!vec) {
-        if (lds > 64 * 1024) VIT_HIP(hipFuncSetAttribute((const void*)ln_bwd_k<TD, ST>,
+        if (lds > 64 * 1024) VIT_HIP(hipFuncSetAttribute((const void*)ln_bwd_k<TD, ST, DP>,
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ln_bwd_k<TD, ST><<<grid, 256, lds, s>>>(io, dout, inp, w, mean, rstd, rows, C);
+        ln_bwd_k<TD, ST, DP><<<grid, 256, lds, s>>>(io, dout, inp, w, mean, rstd, rows, C);
     } else {
 #define VIT_LNB(NV)                                                                                        \
-    if (lds > 64 * 1024) VIT_HIP(hipFuncSetAttribute((const void*)ln_bwd_vec_k<NV, TD, ST>,                 \
+    if (lds > 64 * 1024) VIT_HIP(hipFuncSetAttribute((const void*)ln_bwd_vec_k<NV, TD, ST, DP>,             \
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    ln_bwd_vec_k<NV, TD, ST><<<grid, 256, lds, s>>>(io, dout, inp, w, mean, rstd, rows, C)
+    ln_bwd_vec_k<NV, TD, ST, DP><<<grid, 256, lds, s>>>(io, dout, inp, w, mean, rstd, rows, C)
         switch (C / 256) {
             case 1: VIT_LNB(1); break;
             case 2: VIT_LNB(2); break;
@@ -884,6 +912,22 @@ void ln_backward_bf16_stream(bf16_t* dres_out, uint8_t* lo_out, const bf16_t* dr
     io.hi_out = dres_out; io.lo_out = lo_out; io.hi_in = dres_in; io.lo_in = lo_in;
     io.dweight = dw; io.dbias = db; io.dsum = dres_colsum; io.part = part;
     ln_backward_any<bf16_t, true>(io, dout, inp, w, mean, rstd, rows, C, s);
+}
+void ln_backward_bf16_stream_dp(bf16_t* dres_out, uint8_t* lo_out, bf16_t* dres_scaled, const float* row_scale,
+                                const bf16_t* dres_in, const uint8_t* lo_in, float* dw, float* db,
+                                float* dres_colsum, const bf16_t* dout, const float* inp, const float* w,
+                                const float* mean, const float* rstd, long long rows, int C, hipStream_t s,
+                                float* part) {
+    if (!dres_out || !lo_out || !dres_in || !lo_in || !dres_scaled || !row_scale) {
+        set_error("layernorm_backward: the row-scaled bf16 stream needs its 5 planes and the row scales");
+        return;
+    }
+    if (((uintptr_t)lo_in | (uintptr_t)lo_out) & 3) { set_error("layernorm_backward: lo8 planes need 4-B alignment"); return; }
+    LnbIo io{};
+    io.hi_out = dres_out; io.lo_out = lo_out; io.hi_in = dres_in; io.lo_in = lo_in;
+    io.dweight = dw; io.dbias = db; io.dsum = dres_colsum; io.part = part;
+    io.rscale = row_scale; io.hi_scaled = dres_scaled;
+    ln_backward_any<bf16_t, true, true>(io, dout, inp, w, mean, rstd, rows, C, s);
 }
 // out[c][r] = in[r][c] for `count` matrices of R x Cc bf16 spaced `stride` elements apart
 // (in and out use the same stride); 64 x 64 tiles through LDS, 16-B global accesses.
@@ -1361,6 +1405,23 @@ void gemm_bf16_fused_rows(void* C, void* C2, long long ldc, const void* aux, lon
     a.colsum_out = colsum_out;
     a.M = M; a.N = N; a.K = K; a.epi = epi;
     a.rows_gathered = rows_gathered != 0; a.colsum_row_period = colsum_row_period;
+    gemm_bf16(a, stream());
+}
+void gemm_bf16_fused_rowscale(void* C, void* C2, long long ldc, const void* aux, long long ldaux,
+                              const uint16_t* A, long long lda, int a_kcontig, const uint16_t* B,
+                              long long ldb, int b_kcontig, const float* bias, float* colsum_out, int M,
+                              int N, int K, int epi, int rows_gathered, int colsum_row_period,
+                              const float* row_scale, long long ld_row_scale) {
+    VIT_REQUIRE(epi == EPI_F32_RESID_RS, "gemm_bf16_fused_rowscale: epi %d (12 = the row-scaled residual)", epi);
+    VIT_REQUIRE(colsum_row_period == 0 && !colsum_out, "gemm_bf16_fused_rowscale: epi 12 sums no columns");
+    VIT_REQUIRE(row_scale && aux && ld_row_scale >= 0, "gemm_bf16_fused_rowscale: aux / row_scale / ld_row_scale");
+    GemmArgs a;
+    a.A = A; a.lda = lda; a.a_kcontig = a_kcontig != 0;
+    a.B = B; a.ldb = ldb; a.b_kcontig = b_kcontig != 0;
+    a.C = C; a.C2 = C2; a.ldc = ldc; a.aux = aux; a.ldaux = ldaux; a.bias = bias;
+    a.M = M; a.N = N; a.K = K; a.epi = epi;
+    a.rows_gathered = rows_gathered != 0;
+    a.row_scale = row_scale; a.ld_row_scale = ld_row_scale;
     gemm_bf16(a, stream());
 }
 void gemm_bf16_set_variant(int variant) { gemm_set_variant(variant); }

@@ -26,6 +26,15 @@ void ln_backward_bf16_stream(bf16_t* dres_out, uint8_t* lo_out, const bf16_t* dr
                              float* dw, float* db, float* dres_colsum, const bf16_t* dout, const float* inp,
                              const float* w, const float* mean, const float* rstd, long long rows, int C,
                              hipStream_t s, float* part = nullptr);
+// stochastic depth: the same, with dres_out also the upstream gradient of a residual
+// branch scaled per row in the forward: dres_scaled = bf16(fl32(row_scale[r] * dres_out)) (a bf16 plane
+// of its own, the branch's GEMM operand) and dres_colsum sums those fp32 products; dres_out / lo_out
+// (the pass-through gradient) keep the bits of ln_backward_bf16_stream
+void ln_backward_bf16_stream_dp(bf16_t* dres_out, uint8_t* lo_out, bf16_t* dres_scaled, const float* row_scale,
+                                const bf16_t* dres_in, const uint8_t* lo_in, float* dw, float* db,
+                                float* dres_colsum, const bf16_t* dout, const float* inp, const float* w,
+                                const float* mean, const float* rstd, long long rows, int C, hipStream_t s,
+                                float* part = nullptr);
 int ln_bwd_blocks(long long rows);
 void convert_f2bf(bf16_t* out, const float* inp, long long n, hipStream_t s);
 void sgd(float* p, const float* g, long long n, float lr, hipStream_t s);

@@ -64,6 +64,26 @@ __global__ void rows_to_bf16_k(bf16_t* __restrict__ out, uint8_t* __restrict__ l
     out[o] = h;
     lo[o] = (uint8_t)lo8_encode(in[i], bf2f(h));
 }
+// ---- stochastic depth
+// the per-row scale table [ntab][B*T] from the per-image one [ntab][B] (ntab = 2 L: layer, branch)
+__global__ void dp_expand_k(float* __restrict__ rows, const float* __restrict__ img, long long n, int T) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        rows[i] = img[i / T];
+}
+// the last block's MLP branch gradient from the head's CLS rows in[b][c], image b scaled by rs[b * ld_rs]:
+// u = fl32(rs * in) into sf[b][c] (fp32: the fcproj_b column sums) and bf16(u) into the CLS rows of the
+// scaled plane out [B, T, C]
+__global__ void rows_to_bf16_rs_k(bf16_t* __restrict__ out, long long ldo, float* __restrict__ sf,
+                                  const float* __restrict__ in, const float* __restrict__ rs, long long ld_rs,
+                                  int rows, int C) {
+#pragma clang fp contract(off)
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= (long long)rows * C) return;
+    const long long b = i / C;
+    const float u = rs[b * ld_rs] * in[i];
+    sf[i] = u;
+    out[b * ldo + (i - b * C)] = f2bf(u);
+}
 // dst [rows][n] += src [rows][lds] (its first n columns)
 __global__ void add_cols_k(float* __restrict__ dst, const float* __restrict__ src, int rows, int n, int lds) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < (long long)rows * n;
@@ -385,6 +405,88 @@ struct Trainer {
     aug::Prepared aug_plan;
     bool aug_pending = false;
     void* aug_scratch = nullptr;
+    // stochastic depth (vit_trainer_set_drop_path): a one-shot table s[l][br][b] of scales for
+    // the residual branches (br 0 = attention, 1 = MLP) of the next training forward and its backward.
+    // dp_pending: set and not yet consumed; dp_fwd: the running forward applies dp_rows; dp_bwd: the last
+    // training forward did (its backward follows it; an eval in between leaves it); dp_used: that table.
+    // Device: dp_img [L][2][B] (uploaded by the setter), dp_rows [L][2][B*T] (expanded when consumed: the
+    // GEMM epilogues and LayerNorm backwards read one scale per row), and in bf16 mode the two scaled bf16
+    // planes dres_s / dres_s2 beside dres_bf / dres_bf2 and dcls_xs [B][C], the head's scaled CLS rows.
+    // All allocated on first use.  The setter copies the host table into one of two pinned staging buffers
+    // and enqueues the upload on s, so it neither waits for the steps in flight nor keeps the caller's
+    // array; a staging buffer is rewritten only after the upload that read it (two tables ago) has run.
+    std::vector<float> dp_pending, dp_used;
+    float* dp_stage[2]{};
+    hipEvent_t dp_staged[2]{};
+    int dp_k = 0;
+    bool dp_has_pending = false, dp_fwd = false, dp_bwd = false, dp_last_used = false;
+    float *dp_img = nullptr, *dp_rows = nullptr, *dcls_xs = nullptr;
+    bf16_t *dres_s = nullptr, *dres_s2 = nullptr;
+    const float* dp_scale(int l, int br, long long r0) const { return dp_rows + ((long long)(l * 2 + br)) * BT + r0; }
+    bool dp_alloc() {
+        if (dp_img) return true;
+        float* a = alloc<float>((long long)L * 2 * B);
+        float* b = alloc<float>((long long)L * 2 * BT);
+        bool ok = a && b;
+        if (ok && lowp()) {
+            dres_s = alloc<bf16_t>(BT * C);
+            dres_s2 = alloc<bf16_t>(BT * C);
+            dcls_xs = alloc<float>((long long)B * C);
+            ok = dres_s && dres_s2 && dcls_xs;
+        }
+        for (int k = 0; k < 2 && ok; k++) {
+            ok = hipHostMalloc((void**)&dp_stage[k], (size_t)L * 2 * B * sizeof(float), hipHostMallocDefault) == hipSuccess &&
+                 hipEventCreateWithFlags(&dp_staged[k], hipEventDisableTiming) == hipSuccess;
+            if (!ok) set_error("trainer: drop-path staging buffers");
+        }
+        if (!ok) return false;
+        dp_rows = b;
+        dp_img = a;
+        return true;
+    }
+    bool set_drop_path(const float* host) {
+        if (fp8()) {
+            set_error("vit_trainer_set_drop_path: not supported in fp8 mode");
+            return false;
+        }
+        if (!host) {
+            dp_has_pending = false;
+            return true;
+        }
+        const size_t n = (size_t)L * 2 * B;
+        for (size_t i = 0; i < n; i++)
+            if (!(std::isfinite(host[i]) && host[i] >= 0.f)) {
+                set_error("vit_trainer_set_drop_path: layer %d branch %d image %d: scale %g is not finite and >= 0",
+                          (int)(i / (2 * (size_t)B)), (int)(i / B % 2), (int)(i % B), (double)host[i]);
+                return false;
+            }
+        if (!dp_alloc()) return false;
+        dp_pending.assign(host, host + n);
+        // the upload runs on the trainer's stream, behind the steps in flight (only the expand kernel of the
+        // next training forward, on s too, reads dp_img), from the pinned copy: the caller's array has been
+        // read when this returns
+        const int k = dp_k++ & 1;
+        VIT_HIP(hipEventSynchronize(dp_staged[k]));  // (never recorded: returns at once)
+        memcpy(dp_stage[k], host, n * sizeof(float));
+        VIT_HIP(hipMemcpyAsync(dp_img, dp_stage[k], n * sizeof(float), hipMemcpyHostToDevice, s));
+        VIT_HIP(hipEventRecord(dp_staged[k], s));
+        if (has_error()) return false;
+        dp_has_pending = true;
+        return true;
+    }
+    // at the start of a forward: a training forward (a batch with labels, not eval) consumes the pending table
+    void dp_begin(bool training) {
+        dp_fwd = false;
+        if (!training) return;
+        dp_fwd = dp_bwd = dp_last_used = dp_has_pending;
+        if (!dp_fwd) return;
+        dp_has_pending = false;
+        dp_used = dp_pending;
+        // every stream of the previous backward has joined s, so nothing still reads dp_rows
+        const long long n = (long long)L * 2 * BT;
+        dp_expand_k<<<grid_for(n, 256), 256, 0, s>>>(dp_rows, dp_img, n, T);
+        after_launch("drop_path_expand");
+    }
     // AdamW state (allocated on the first AdamW step / a checkpoint load with optimizer state)
     float *adam_m = nullptr, *adam_v = nullptr;
     int adam_t = 0;
@@ -943,6 +1045,10 @@ struct Trainer {
         if (s2) (void)hipStreamSynchronize(s2);
         for (int k = 1; k < MAXMB; k++) if (ms[k]) (void)hipStreamSynchronize(ms[k]);
         if (comm) ncclCommDestroy(comm);
+        for (int k = 0; k < 2; k++) {
+            if (dp_stage[k]) (void)hipHostFree(dp_stage[k]);
+            if (dp_staged[k]) (void)hipEventDestroy(dp_staged[k]);
+        }
         for (auto& a : allocs) (void)hipFree(a.p);
         for (auto e : chunk_ev) (void)hipEventDestroy(e);
         for (auto e : chunk_ev2) (void)hipEventDestroy(e);
@@ -1331,6 +1437,9 @@ struct Trainer {
                 pr.A = a.atty + r0 * C; pr.lda = rs * C; pr.B = W(P_ATTPROJW, l); pr.ldb = C; pr.C = a.res2 + r0 * C;
                 pr.ldc = rs * C; pr.bias = P(P_ATTPROJB, l); pr.aux = x; pr.ldaux = rs * C;
                 pr.M = Mr; pr.N = C; pr.K = C; pr.epi = EPI_F32_RESID; pr.rows_gathered = lcg;
+                if (dp_fwd) {  // res2 = x + fl32(s * attproj(..)): the row scales at the rows' stride
+                    pr.epi = EPI_F32_RESID_RS; pr.row_scale = dp_scale(l, 0, r0); pr.ld_row_scale = rs;
+                }
                 gemm_w(TC_PROJ_FWD, pr, P_ATTPROJW, l, false, mb, st, PRE_NONE, false, rc ? &c_atty : nullptr);
                 tbeg(TC_LN_FWD, 0, st);
                 if (lm)
@@ -1357,6 +1466,9 @@ struct Trainer {
                 fp.A = a.fchg + r0 * 4 * C; fp.lda = rs * 4 * C; fp.B = W(P_FCPROJW, l); fp.ldb = 4 * C;
                 fp.C = a.res3 + r0 * C; fp.ldc = rs * C; fp.bias = P(P_FCPROJB, l); fp.aux = a.res2 + r0 * C;
                 fp.ldaux = rs * C; fp.M = Mr; fp.N = C; fp.K = 4 * C; fp.epi = EPI_F32_RESID; fp.rows_gathered = lcg;
+                if (dp_fwd) {
+                    fp.epi = EPI_F32_RESID_RS; fp.row_scale = dp_scale(l, 1, r0); fp.ld_row_scale = rs;
+                }
                 gemm_w(TC_FCPROJ_FWD, fp, P_FCPROJW, l, false, mb, st, fuse_mx ? PRE_EPI : PRE_NONE);
             }
         }
@@ -1457,7 +1569,24 @@ struct Trainer {
         //   fc_b     += colsum(dfch):  fcproj dgrad epilogue
         //   attproj_b+= colsum(dres2): LN2-backward
         //   qkv_b    += colsum(dqkv):  attention backward
-        colsum_f32(G(P_FCPROJB, L - 1), dcls_x, B, C, C, s, red_ws);
+        // stochastic depth: the pass-through gradient stays rbA / rbB; each branch's GEMMs
+        // read a second bf16 plane, bf16(fl32(s * dres)), and its last bias gradient sums the fp32 products.
+        // sA / sB are written by the kernels that write rbA / rbB (the LayerNorm backwards; the head's rows
+        // below), on the same streams, and read by the same GEMMs, so the EV_RESA / EV_RESB / after_wgrad
+        // ordering of rbA / rbB orders them too.  Off the CLS rows of the last block they are exact zeros,
+        // as rbA / rbB are (0 * s), so last_cls and last_cls_bwd hold unchanged.
+        const bool dp = dp_bwd;
+        const bf16_t* sA = dp ? dres_s : rbA;   // the fcproj dgrad's / wgrad's dout
+        const bf16_t* sB = dp ? dres_s2 : rbB;  // the attproj dgrad's / wgrad's dout
+        if (dp) {
+            VIT_HIP(hipMemsetAsync(dres_s, 0, (size_t)BT * C * 2, s));
+            rows_to_bf16_rs_k<<<cdiv((long long)B * C, 256), 256, 0, s>>>(dres_s, (long long)T * C, dcls_xs, dcls_x,
+                                                                         dp_scale(L - 1, 1, 0), T, B, C);
+            after_launch("drop_path_head_rows");
+            colsum_f32(G(P_FCPROJB, L - 1), dcls_xs, B, C, C, s, red_ws);
+        } else {
+            colsum_f32(G(P_FCPROJB, L - 1), dcls_x, B, C, C, s, red_ws);
+        }
         mb_fork();
         const int Bm = B / nmb;
         const long long R = (long long)Bm * T;
@@ -1486,16 +1615,16 @@ struct Trainer {
             // fcproj: dfch = (dres3 . fcprojw) * gelu'(fch) (stored as fchd);  fcprojw += dres3^T . fchg
             const bool ec = epicol_on();
             QMat c_fchg = ec ? fchgc_of(l) : QMat{};
-            if (!rc) wgrad(TC_FCPROJ_WGRAD, rbA, C, a.fchg, 4 * C, G(P_FCPROJW, l), EV_RESA, EV_W1, nullptr, nullptr, kper);
+            if (!rc) wgrad(TC_FCPROJ_WGRAD, sA, C, a.fchg, 4 * C, G(P_FCPROJW, l), EV_RESA, EV_W1, nullptr, nullptr, kper);
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 after_wgrad(EV_W2, ms[mb]);  // the previous layer's fc wgrad has read dfch
                 GemmArgs d1, d1g;
                 // (last_cls_bwd = 2 in the last block: on the CLS rows, where this step's clears covered it)
-                if (lc && d1_clean && !ec && lc_d1_gathered(l, mb, rbA, d1g)) {
+                if (lc && d1_clean && !ec && lc_d1_gathered(l, mb, sA, d1g)) {
                     d1 = d1g;
                 } else {
-                    d1.A = rbA + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C, 4 * C);
+                    d1.A = sA + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C, 4 * C);
                     d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
                     d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
                     fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
@@ -1532,6 +1661,12 @@ struct Trainer {
                                                act_q[mb], act_s[mb], dcol[1].q, dcol[1].s, kp_tok, r0, mb_ntok(mb, R),
                                                lnb_scr[mb]);
                     if (two_streams) VIT_HIP(hipEventRecord(mev[mb][EV_RESB], ms[mb]));
+                } else if (dp) {  // + dres2 scaled by the attention branch's rows; attproj_b from the products
+                    ln_backward_bf16_stream_dp(rbB + r0 * C, loB + r0 * C, dres_s2 + r0 * C, dp_scale(l, 0, r0),
+                                               rbA + r0 * C, loA + r0 * C, G(P_LN2W, l), G(P_LN2B, l),
+                                               G(P_ATTPROJB, l), dln_bf + r0 * C, a.res2 + r0 * C, P(P_LN2W, l),
+                                               a.ln2_mean + r0, a.ln2_rstd + r0, R, C, ms[mb],
+                                               sg_rows(l, sg_ln2) + (long long)mb * ln_bwd_blocks(R) * 3 * C);
                 } else {
                     ln_backward_bf16_stream(rbB + r0 * C, loB + r0 * C, rbA + r0 * C, loA + r0 * C, G(P_LN2W, l),
                                             G(P_LN2B, l), G(P_ATTPROJB, l), dln_bf + r0 * C, a.res2 + r0 * C,
@@ -1541,11 +1676,11 @@ struct Trainer {
                 tend();
             }
             // attproj
-            if (!rc) wgrad(TC_PROJ_WGRAD, rbB, C, a.atty, C, G(P_ATTPROJW, l), EV_RESB, EV_W3, nullptr, nullptr, kper);
+            if (!rc) wgrad(TC_PROJ_WGRAD, sB, C, a.atty, C, G(P_ATTPROJW, l), EV_RESB, EV_W3, nullptr, nullptr, kper);
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d3;
-                d3.A = rbB + r0 * C; d3.lda = rs * C; dgrad_b(d3, P_ATTPROJW, l, C, C);
+                d3.A = sB + r0 * C; d3.lda = rs * C; dgrad_b(d3, P_ATTPROJW, l, C, C);
                 d3.C = datty + r0 * C; d3.ldc = rs * C; d3.M = Mr; d3.N = C; d3.K = C; d3.epi = EPI_BF16_STORE;
                 d3.rows_gathered = lcg;
                 gemm_w(TC_PROJ_DGRAD, d3, P_ATTPROJW, l, true, mb, ms[mb], lbm ? PRE_LN : PRE_NONE, false,
@@ -1579,6 +1714,12 @@ struct Trainer {
                                                act_q[mb], act_s[mb], dcol[0].q, dcol[0].s, kp_tok, r0, mb_ntok(mb, R),
                                                lnb_scr[mb]);
                     if (two_streams) VIT_HIP(hipEventRecord(mev[mb][EV_RESA], ms[mb]));
+                } else if (dp && l > 0) {  // + dres3 of layer l-1 scaled by its MLP branch's rows; its fcproj_b
+                    ln_backward_bf16_stream_dp(rbA + r0 * C, loA + r0 * C, dres_s + r0 * C, dp_scale(l - 1, 1, r0),
+                                               rbB + r0 * C, loB + r0 * C, G(P_LN1W, l), G(P_LN1B, l),
+                                               G(P_FCPROJB, l - 1), dln_bf + r0 * C, xl + r0 * C, P(P_LN1W, l),
+                                               a.ln1_mean + r0, a.ln1_rstd + r0, R, C, ms[mb],
+                                               sg_rows(l, sg_ln1) + (long long)mb * ln_bwd_blocks(R) * 3 * C);
                 } else {
                     ln_backward_bf16_stream(rbA + r0 * C, loA + r0 * C, rbB + r0 * C, loB + r0 * C, G(P_LN1W, l),
                                             G(P_LN1B, l), l > 0 ? G(P_FCPROJB, l - 1) : nullptr, dln_bf + r0 * C,
@@ -1656,12 +1797,14 @@ struct Trainer {
             mm_fwd(a.qkvf, a.ln1f, P(P_QKVW, l), P(P_QKVB, l), C, 3 * C);
             attn_forward_f32(a.attyf, a.preatt, a.att, a.qkvf, B, T, C, NH, s);
             mm_fwd(a.attproj, a.attyf, P(P_ATTPROJW, l), P(P_ATTPROJB, l), C, C);
-            add(a.res2, x, a.attproj, BT * C);
+            if (dp_fwd) add_rs(a.res2, x, a.attproj, dp_scale(l, 0, 0), BT * C);
+            else add(a.res2, x, a.attproj, BT * C);
             ln_forward_f32(a.ln2f, a.ln2_mean, a.ln2_rstd, a.res2, P(P_LN2W, l), P(P_LN2B, l), BT, C, s);
             mm_fwd(a.fchf, a.ln2f, P(P_FCW, l), P(P_FCB, l), C, 4 * C);
             gelu(a.fchgf, a.fchf, BT * 4 * C);
             mm_fwd(a.fcproj, a.fchgf, P(P_FCPROJW, l), P(P_FCPROJB, l), 4 * C, C);
-            add(a.res3, a.res2, a.fcproj, BT * C);
+            if (dp_fwd) add_rs(a.res3, a.res2, a.fcproj, dp_scale(l, 1, 0), BT * C);
+            else add(a.res3, a.res2, a.fcproj, BT * C);
         }
         head_forward();
     }
@@ -1688,6 +1831,9 @@ struct Trainer {
     void gelu(float* out, const float* in, long long n);
     void gelu_bwd(float* dinp, const float* in, const float* dout, long long n);
     void res_bwd(float* d1, float* d2, const float* dout, long long n);
+    // stochastic depth: out = a + fl32(rs[row] * b);  d1 += dout, d2 += fl32(rs[row] * dout)  (rows of C)
+    void add_rs(float* out, const float* a, const float* b, const float* rs, long long n);
+    void res_bwd_rs(float* d1, float* d2, const float* dout, const float* rs, long long n);
 
     void backward_f32() {
         float* dcur = dres_a;
@@ -1700,13 +1846,15 @@ struct Trainer {
             VIT_HIP(hipMemsetAsync(g_block, 0, g_block_elems * 4, s));
             VIT_HIP(hipMemsetAsync(dnxt, 0, BT * C * 4, s));
             // train_vit.rs:359-368
-            res_bwd(g_dres2, g_dfcproj, dcur, BT * C);
+            if (dp_bwd) res_bwd_rs(g_dres2, g_dfcproj, dcur, dp_scale(l, 1, 0), BT * C);
+            else res_bwd(g_dres2, g_dfcproj, dcur, BT * C);
             mm_bwd(g_dfchg, G(P_FCPROJW, l), G(P_FCPROJB, l), g_dfcproj, a.fchgf, P(P_FCPROJW, l), 4 * C, C);
             gelu_bwd(g_dfch, a.fchf, g_dfchg, BT * 4 * C);
             mm_bwd(g_dln2, G(P_FCW, l), G(P_FCB, l), g_dfch, a.ln2f, P(P_FCW, l), C, 4 * C);
             ln_backward_f32(g_dres2, G(P_LN2W, l), G(P_LN2B, l), g_dln2, a.res2, P(P_LN2W, l),
                             a.ln2_mean, a.ln2_rstd, BT, C, s, red_ws);
-            res_bwd(dnxt, g_dattproj, g_dres2, BT * C);
+            if (dp_bwd) res_bwd_rs(dnxt, g_dattproj, g_dres2, dp_scale(l, 0, 0), BT * C);
+            else res_bwd(dnxt, g_dattproj, g_dres2, BT * C);
             mm_bwd(g_datty, G(P_ATTPROJW, l), G(P_ATTPROJB, l), g_dattproj, a.attyf, P(P_ATTPROJW, l), C, C);
             attn_backward_f32(g_dqkv, g_dpreatt, g_datt, g_datty, a.qkvf, a.att, B, T, C, NH, s);
             mm_bwd(g_dln1, G(P_QKVW, l), G(P_QKVB, l), g_dqkv, a.ln1f, P(P_QKVW, l), C, 3 * C);
@@ -2147,6 +2295,31 @@ __global__ void resbwd_k(float* d1, float* d2, const float* g, long long n) {
         d2[i] += g[i];
     }
 }
+// stochastic depth, fp32 mode: the residual add and its backward with the branch scaled
+// per row (rs[i / C]); every product rounded to fp32 on its own
+__global__ void add_rs_k(float* o, const float* a, const float* b, const float* rs, long long n, int C) {
+#pragma clang fp contract(off)
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float y = rs[i / C] * b[i];
+        o[i] = a[i] + y;
+    }
+}
+__global__ void resbwd_rs_k(float* d1, float* d2, const float* g, const float* rs, long long n, int C) {
+#pragma clang fp contract(off)
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float y = rs[i / C] * g[i];
+        d1[i] += g[i];
+        d2[i] += y;
+    }
+}
+void Trainer::add_rs(float* out, const float* a, const float* b, const float* rs, long long n) {
+    add_rs_k<<<grid_for(n, 256), 256, 0, s>>>(out, a, b, rs, n, C);
+    after_launch("residual_forward_rowscale");
+}
+void Trainer::res_bwd_rs(float* d1, float* d2, const float* dout, const float* rs, long long n) {
+    resbwd_rs_k<<<grid_for(n, 256), 256, 0, s>>>(d1, d2, dout, rs, n, C);
+    after_launch("residual_backward_rowscale");
+}
 void Trainer::add(float* out, const float* a, const float* b, long long n) {
     add_k<<<grid_for(n, 256), 256, 0, s>>>(out, a, b, n);
     after_launch("residual_forward");
@@ -2292,8 +2465,54 @@ int vit_trainer_get_pixels(vit_trainer_t* h, float* host) {
 int vit_trainer_forward(vit_trainer_t* h, int b_global) {
     auto& t = h->t;
     t.b_global = b_global > 0 ? b_global : t.B;
+    t.dp_begin(t.has_targets);
     if (t.lowp()) t.forward_bf16(); else t.forward_f32();
+    t.dp_fwd = false;
     return vit::has_error();
+}
+int vit_trainer_set_drop_path(vit_trainer_t* h, const float* host_scales) {
+    if (!h) {
+        set_error("vit_trainer_set_drop_path: null trainer");
+        return 1;
+    }
+    return h->t.set_drop_path(host_scales) ? 0 : 1;
+}
+// host-only: the project's counter-form splitmix64 (loader.hip, augment.hip), tag "droppath"
+static unsigned long long dp_sm64(unsigned long long seed, unsigned long long i) {
+    unsigned long long z = seed + (i + 1) * 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+int vit_drop_path_draw(unsigned long long seed, long long key, int num_layers, int batch, float rate, int linear,
+                       float* out) {
+    if (!out || num_layers < 1 || batch < 1 || !(rate >= 0.f && rate < 1.f)) {
+        set_error("vit_drop_path_draw: bad arguments (num_layers %d, batch %d, rate %g of [0, 1))", num_layers, batch,
+                  (double)rate);
+        return 1;
+    }
+    const unsigned long long s = seed ^ dp_sm64(0x64726f7070617468ULL, (unsigned long long)key);
+    for (int l = 0; l < num_layers; l++) {
+        const float p = linear && num_layers > 1 ? (float)((double)rate * l / (num_layers - 1)) : rate;
+        const float keep_scale = 1.0f / (1.0f - p);
+        for (int br = 0; br < 2; br++)
+            for (int b = 0; b < batch; b++) {
+                const unsigned long long pos = (unsigned long long)(2 * l + br) * (unsigned long long)batch + b;
+                const float u = (float)(dp_sm64(s, pos) >> 40) * (1.0f / 16777216.0f);
+                out[((size_t)l * 2 + br) * batch + b] = u >= p ? keep_scale : 0.0f;
+            }
+    }
+    return 0;
+}
+int vit_trainer_get_drop_path(vit_trainer_t* h, float* out, int* used) {
+    if (!h) {
+        set_error("vit_trainer_get_drop_path: null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    if (used) *used = t.dp_last_used ? 1 : 0;
+    if (out && t.dp_last_used) memcpy(out, t.dp_used.data(), t.dp_used.size() * sizeof(float));
+    return 0;
 }
 int vit_trainer_zero_grad(vit_trainer_t* h) {
     auto& t = h->t;
@@ -2429,6 +2648,7 @@ int vit_trainer_eval(vit_trainer_t* h, int* host_pred, int* host_correct) {
     auto& t = h->t;
     if (host_correct) *host_correct = -1;
     t.b_global = t.B;
+    t.dp_begin(false);  // eval never drops (a pending table stays pending)
     if (t.lowp()) t.forward_bf16(); else t.forward_f32();
     VIT_HIP(hipMemsetAsync(t.preds + t.B, 0, 4, t.s));
     vit::argmax_rows_k<<<cdiv(t.B, 4), 256, 0, t.s>>>(t.preds, t.preds + t.B, t.logits,
