@@ -15,13 +15,18 @@
  *     [4] num_layers  [5] num_heads  [6] channels   (header[4..6], as the reference)
  *     [7] img  [8] patch  [9] in_ch
  *     [10] flags: bit 0 = AdamW state (m, v) follows the parameters
+ *                 bit 1 = an EMA of the weights follows them (behind m and v when bit 0 is set too)
  *     [11] AdamW step t (number of completed AdamW updates)
  *     [12] / [13] num_params, low / high 32 bits
  *     [14..17] beta1, beta2, eps, weight_decay of the last AdamW update (IEEE fp32 bits)
+ *     [18] the EMA's decay (IEEE fp32 bits)   [19] / [20] its update count, low / high 32 bits
+ *          (all three zero unless flags bit 1 is set)
  *     rest zero
  *   fp32 params[num_params] at byte 1024, in the 20-tensor canonical order of vit_trainer.h
  *   (patch_w, patch_b, cls, wpe, ln1w .. fcprojb (each [L, ...]), lnfw, lnfb, head_w, head_b)
  *   if flags & 1: fp32 m[num_params], then fp32 v[num_params], same order.
+ *   if flags & 2: fp32 ema[num_params], same order.
+ * A file without an EMA has the bytes it had before bit 1 existed; the version stays 1.
  *
  * All functions return 0 on success; on failure non-zero with the reason in vit_last_error().
  */
@@ -50,19 +55,33 @@ typedef struct {
 
 /* canonical parameter count of a config (sum of the 20 tensor sizes) */
 long long vit_config_num_params(const vit_config_t* cfg);
-/* header only; validates magic, version, T == (img/patch)^2+1 and the file size */
+/* header only; validates magic, version, T == (img/patch)^2+1 and the file size (of either layout: with
+ * or without the EMA array, which this struct does not report: vit_checkpoint_read_ema) */
 int vit_checkpoint_read_info(const char* path, vit_checkpoint_info_t* info);
 /* m, v: NULL for a parameters-only file (then step / adamw are ignored) */
 int vit_checkpoint_write(const char* path, const vit_config_t* cfg, const float* params,
                          const float* m, const float* v, int step, const vit_adamw_t* adamw);
 /* reads params (and m, v when non-NULL and present in the file) of num_params elements; fails if
- * the file's config differs from *cfg */
+ * the file's config differs from *cfg.  An EMA array in the file is ignored. */
 int vit_checkpoint_read(const char* path, const vit_config_t* cfg, float* params, float* m,
                         float* v);
+/* vit_checkpoint_write with an EMA of the weights: ema NULL writes exactly the file vit_checkpoint_write does
+ * (ema_decay / ema_updates ignored); otherwise ema[num_params] follows the other arrays and the header
+ * carries ema_decay and ema_updates (>= 0) */
+int vit_checkpoint_write_ex(const char* path, const vit_config_t* cfg, const float* params,
+                            const float* m, const float* v, int step, const vit_adamw_t* adamw,
+                            const float* ema, float ema_decay, long long ema_updates);
+/* *has_ema = 1 if the file holds an EMA, then *decay, *updates from the header and ema[num_params] (NULL: query
+ * only); without one *has_ema = 0, *decay = 0, *updates = 0 and ema is left alone.  Every out pointer may be
+ * NULL.  Fails if the file's config differs from *cfg. */
+int vit_checkpoint_read_ema(const char* path, const vit_config_t* cfg, float* ema, float* decay,
+                            long long* updates, int* has_ema);
 
 /* ---- trainer-level save / resume (synchronous).  Save writes the AdamW state once an AdamW
- *      step has run; load restores params (and m, v, t when present) and refreshes the bf16
- *      shadows. ---- */
+ *      step has run, and the EMA (vit_trainer_set_ema) while it is on; load restores params (and m, v, t
+ *      when present) and refreshes the bf16 shadows.  Loading a file with an EMA turns EMA on with the
+ *      file's decay, values and update count; loading one without into a trainer whose EMA is on seeds the
+ *      average again from the loaded parameters (count 0). ---- */
 int vit_trainer_save_checkpoint(vit_trainer_t* t, const char* path);
 int vit_trainer_load_checkpoint(vit_trainer_t* t, const char* path);
 

@@ -66,6 +66,8 @@ enum {
     VIT_HIT_LNB_MX = 90,             /* LayerNorm backward (residual-gradient stream) + both MX forms (fp8) */
     VIT_HIT_AUGMENT = 91,            /* RandAugment on the uint8 batch: + 0 statistics / LUT, 1 in-place apply,
                                         2 out-of-place apply (sharpness, affine), 3 copy back */
+    VIT_HIT_EMA = 95,                /* a launch that advances an EMA of the weights: an optimizer kernel's EMA
+                                        instantiation (vit_trainer_set_ema) or ema_update */
     VIT_HIT_COUNT = 96
 };
 int vit_kernel_hits(long long* out, int n); /* copies min(n, VIT_HIT_COUNT); returns VIT_HIT_COUNT */
@@ -142,6 +144,12 @@ void sgd_step(float* params, const float* grads, long long n, float lr);
  * Deterministic: per-workgroup partial sums (their number a function of n alone) combined in a
  * fixed order, no floating-point atomics: two calls on the same buffer give the same bits. */
 void grad_sumsq(double* out, const float* x, long long n);
+/* ema[i] = fl32( fl32(decay * ema[i]) + fl32(omd * params[i]) ) for i < n, omd = (float)(1.0 - (double)decay):
+ * numpy's fp32 `decay * ema + omd * params`, each product and the sum rounded on its own (no FMA).  Device
+ * pointers, any n >= 0; 16-byte accesses over n / 4 float4s when both pointers are 16-byte aligned and a
+ * scalar tail for n % 4 (all scalar otherwise).  No reference counterpart: the update the trainer's optimizer
+ * kernels fuse for vit_trainer_set_ema, stand-alone; fp32-mode SGD launches it. */
+void ema_update(float* ema, const float* params, long long n, float decay);
 
 /* ------------------------------------------------------------------ bf16 fast path
  * Build-side extensions with the same conventions; bf16 storage as raw uint16_t, fp32

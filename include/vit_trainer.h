@@ -172,6 +172,40 @@ int vit_trainer_get_drop_path(vit_trainer_t* t, float* out, int* used);
  * [0, 1) (or a bad size): non-zero + vit_last_error. */
 int vit_drop_path_draw(unsigned long long seed, long long key, int num_layers, int batch, float rate,
                        int linear, float* out);
+/* ---- exponential moving average of the weights (timm's ModelEmaV2): one more fp32 arena e,
+ *      advanced by every optimizer step while on.  With d the decay and omd = (float)(1.0 - (double)d), taken
+ *      once on the host, for every element
+ *          e' = fl32( fl32(d * e) + fl32(omd * p') )
+ *      with p' the fp32 master value the step has just written; each product and the sum rounded to fp32 on
+ *      its own (no FMA): numpy's fp32 `d * e + omd * p`.  In bf16 / fp8 mode (and for AdamW in every mode) the
+ *      update runs inside the optimizer kernels, which hold p' in registers; fp32-mode SGD launches
+ *      ema_update (vit_ops.h) behind its update on the same stream: the same bits.  A trainer that never turns
+ *      EMA on issues the launches, allocates the memory and writes the checkpoint bytes it always did.
+ *      Data parallelism needs nothing more: every rank holds identical parameters after a step and applies
+ *      the same elementwise update, so the averages are identical too (every rank must set the same decay). ---- */
+/* decay 0 = off (the default), 0 < decay < 1 = on; NaN, negative or >= 1: non-zero + vit_last_error and the
+ * previous setting stays.  The first switch from off to on allocates the arena (arena_elems floats, counted in
+ * vit_trainer_device_bytes from then on), seeds it with a device copy of the current parameters and sets the
+ * update count to 0; it waits for the steps in flight.  A call while on only changes d (no wait, no re-seed:
+ * a host-side warm-up schedule may call it before every step).  Switching off keeps the arena; the next
+ * switch on seeds it again.  vit_trainer_step, vit_trainer_step_adamw and vit_trainer_train_step advance the
+ * average once per call while on (also at lr = 0, and for tensors frozen by lr_mul = 0); vit_trainer_set_params
+ * does not touch it. */
+int vit_trainer_set_ema(vit_trainer_t* t, float decay);
+/* *decay (0 while off), *updates (optimizer steps averaged since the seed), *on; any pointer may be NULL */
+int vit_trainer_get_ema_info(vit_trainer_t* t, float* decay, long long* updates, int* on);
+/* canonical host copy of the average / overwrite it from one; synchronous; an error while EMA is off */
+int vit_trainer_get_ema(vit_trainer_t* t, float* host);
+int vit_trainer_set_ema_params(vit_trainer_t* t, const float* host);
+/* evaluate with the averaged weights.  on = 1 exchanges the live and the averaged arena (a pointer exchange)
+ * and refreshes every derived copy (the bf16 shadow, the transposed copies, the fp8 MX copies): until on = 0,
+ * vit_trainer_eval / _forward / _get_logits use the average and vit_trainer_get_params returns it, and
+ * vit_trainer_backward, _step, _step_adamw, _train_step, _zero_grad, _set_params, _set_ema, _set_ema_params,
+ * _load_checkpoint and _save_checkpoint return non-zero ("... EMA weights in use") and change nothing.
+ * on = 0 exchanges back and refreshes again: the live fp32 parameters keep their bits and the derived
+ * copies, deterministic functions of them, get theirs back.  on = 1 twice, on = 0 while not in use, and
+ * on = 1 while EMA is off are errors.  Synchronous; waits for the side streams' work first. */
+int vit_trainer_ema_weights(vit_trainer_t* t, int on);
 /* canonical host copies of m, v (either may be NULL) and the step count; synchronous */
 int vit_trainer_get_adamw_state(vit_trainer_t* t, float* m, float* v, int* step);
 /* eval: forward of the current batch, then top-1 per image on the device.
@@ -238,6 +272,9 @@ int vit_trainer_set_concurrency(vit_trainer_t* t, int on);
  *      gradients skip the K-steps of the token axis that hold no CLS row, 2 = also its fcproj input
  *      gradient on the CLS rows, the fc-bias column sums kept in the full-size grouping (same bits
  *      again).  0: both full size,
+ *      "ema_fused" = 1 (default): with EMA on (vit_trainer_set_ema) the bf16 / fp8 optimizer kernels and AdamW
+ *      advance the average themselves; 0 runs them as without EMA and launches ema_update behind each on
+ *      the same stream (same bits; the A/B of tools/bench_ema.py),
  *      "dp_probe" = 1: every gradient chunk is also copied, on the all-reduce stream right after
  *      its all-reduce, into a snapshot arena (read with vit_trainer_get_dp_snapshot) — a check
  *      that each overlapped chunk was final when it was reduced.

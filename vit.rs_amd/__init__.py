@@ -10,6 +10,7 @@ There is no CPU fallback: if libvit_hip.so is missing or cannot be loaded, every
 raises.  If torch is used in the same process, import it BEFORE this package so that the
 HIP runtime torch ships is the single runtime in the process.
 """
+import contextlib
 import ctypes
 import os
 import sys
@@ -24,6 +25,7 @@ from . import mix  # noqa: E402  (mixup / cutmix draws and their numpy statement
 from . import groups  # noqa: E402  (parameter-group tables: no_decay, layer_decay)
 from . import augment  # noqa: E402  (RandAugment: the policy draw and its numpy statement)
 from . import droppath  # noqa: E402  (stochastic depth: the per-step table draw)
+from . import ema  # noqa: E402  (EMA of the weights: the warm-up schedule and the numpy statement)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
@@ -96,6 +98,7 @@ _SIGS = {
     "patch_embed_backward": (None, [P, P, P, P, P, P, I, I, I, I]),
     "sgd_step": (None, [P, P, LL, F]),
     "grad_sumsq": (None, [P, P, LL]),
+    "ema_update": (None, [P, P, LL, F]),
     # bf16 extensions
     "matmul_forward_bf16": (None, [P, P, P, P, I, I, I, I]),
     "matmul_backward_bf16": (None, [P, P, P, P, P, P, I, I, I, I]),
@@ -158,6 +161,10 @@ _SIGS = {
     "vit_trainer_set_param_groups": (I, [P, P, P]),
     "vit_trainer_get_param_groups": (I, [P, P, P, ctypes.POINTER(I)]),
     "vit_trainer_eval": (I, [P, P, ctypes.POINTER(I)]),
+    "vit_trainer_set_ema": (I, [P, F]), "vit_trainer_get_ema": (I, [P, P]),
+    "vit_trainer_set_ema_params": (I, [P, P]),
+    "vit_trainer_get_ema_info": (I, [P, ctypes.POINTER(F), ctypes.POINTER(LL), ctypes.POINTER(I)]),
+    "vit_trainer_ema_weights": (I, [P, I]),
     "vit_trainer_set_drop_path": (I, [P, P]),
     "vit_trainer_get_drop_path": (I, [P, P, ctypes.POINTER(I)]),
     "vit_drop_path_draw": (I, [ctypes.c_ulonglong, LL, I, I, F, I, P]),
@@ -166,6 +173,9 @@ _SIGS = {
     "vit_checkpoint_read_info": (I, [ctypes.c_char_p, P]),
     "vit_checkpoint_write": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, P, P, I, P]),
     "vit_checkpoint_read": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, P, P]),
+    "vit_checkpoint_write_ex": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, P, P, I, P, P, F, LL]),
+    "vit_checkpoint_read_ema": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, ctypes.POINTER(F),
+                                    ctypes.POINTER(LL), ctypes.POINTER(I)]),
     # input pipeline (include/vit_data.h)
     "vit_loader_open": (P, [ctypes.c_char_p, ctypes.c_char_p, I, I, ctypes.c_ulonglong, I, I, I, I, I]),
     "vit_loader_num_records": (LL, [P]), "vit_loader_steps_per_epoch": (I, [P]),
@@ -227,6 +237,7 @@ HIT_GEMM_PP = 88
 HIT_LN_MX = 89
 HIT_LNB_MX = 90
 HIT_AUGMENT = 91  # + 0 statistics / LUT, 1 in-place apply, 2 out-of-place apply, 3 copy back
+HIT_EMA = 95  # a launch that advances an EMA of the weights (fused optimizer kernel or ema_update)
 
 
 def kernel_hits():
@@ -359,13 +370,15 @@ def checkpoint_info(path):
             "adamw": (info.adamw.beta1, info.adamw.beta2, info.adamw.eps, info.adamw.weight_decay)}
 
 
-def write_checkpoint(path, cfg, params, m=None, v=None, step=0, adamw=None):
-    """Write canonical fp32 params (+ AdamW m, v) in the checkpoint format; host-only."""
+def write_checkpoint(path, cfg, params, m=None, v=None, step=0, adamw=None, ema=None, ema_decay=0.0,
+                     ema_updates=0):
+    """Write canonical fp32 params (+ AdamW m, v; + an EMA of the weights with its decay and update
+    count) in the checkpoint format; host-only.  Without `ema` the file is the one it always was."""
     params = np.ascontiguousarray(params, dtype=np.float32)
     assert params.size == cfg.num_params()
     ptrs = [params.ctypes.data_as(P)]
     keep = []
-    for a in (m, v):
+    for a in (m, v, ema):
         if a is None:
             ptrs.append(None)
         else:
@@ -374,9 +387,32 @@ def write_checkpoint(path, cfg, params, m=None, v=None, step=0, adamw=None):
             keep.append(a)
             ptrs.append(a.ctypes.data_as(P))
     hp = AdamWC(*adamw) if adamw is not None else None
-    if lib().vit_checkpoint_write(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs, int(step),
-                                  ctypes.byref(hp) if hp is not None else None):
+    hp_ref = ctypes.byref(hp) if hp is not None else None
+    if ema is None:
+        rc = lib().vit_checkpoint_write(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step), hp_ref)
+    else:
+        rc = lib().vit_checkpoint_write_ex(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step),
+                                           hp_ref, ptrs[3], float(ema_decay), int(ema_updates))
+    if rc:
         check("write_checkpoint")
+        raise VitError("write_checkpoint failed")
+
+
+def read_checkpoint_ema(path, cfg):
+    """(ema, decay, updates) of a checkpoint written for cfg; (None, 0.0, 0) for a file without an EMA."""
+    d, u, has = F(), LL(), I()
+    c = _cfg_c(cfg)
+    if lib().vit_checkpoint_read_ema(os.fsencode(path), ctypes.byref(c), None, ctypes.byref(d), ctypes.byref(u),
+                                     ctypes.byref(has)):
+        check("read_checkpoint_ema")
+        raise VitError("read_checkpoint_ema failed")
+    if not has.value:
+        return None, 0.0, 0
+    e = np.empty(cfg.num_params(), np.float32)
+    if lib().vit_checkpoint_read_ema(os.fsencode(path), ctypes.byref(c), e.ctypes.data_as(P), None, None, None):
+        check("read_checkpoint_ema")
+        raise VitError("read_checkpoint_ema failed")
+    return e, float(d.value), int(u.value)
 
 
 def read_checkpoint(path, cfg):
@@ -758,6 +794,42 @@ class ViT:
         self._ok(lib().vit_trainer_get_drop_path(self.h, out.ctypes.data_as(P), ctypes.byref(used)),
                  "get_drop_path")
         return out if used.value else None
+
+    # ---- EMA of the weights (include/vit_trainer.h)
+    def set_ema(self, decay):
+        """0 = off; 0 < decay < 1 = on: the first enabling allocates the average and seeds it with the
+        current parameters; later calls only change the decay (ema.warmup_decay before each step).  Every
+        optimizer step then advances it on the device (vit_trainer_set_ema)."""
+        self._ok(lib().vit_trainer_set_ema(self.h, float(decay)), "set_ema")
+
+    def ema(self):
+        """The averaged weights, canonical order (vit_trainer_get_ema; synchronous; raises while off)."""
+        out = np.empty(self.num_parameters, dtype=np.float32)
+        self._ok(lib().vit_trainer_get_ema(self.h, out.ctypes.data_as(P)), "get_ema")
+        return out
+
+    def set_ema_params(self, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        assert flat.size == self.num_parameters
+        self._ok(lib().vit_trainer_set_ema_params(self.h, flat.ctypes.data_as(P)), "set_ema_params")
+
+    def ema_info(self):
+        """(decay, updates, on)"""
+        d, u, on = F(), LL(), I()
+        self._ok(lib().vit_trainer_get_ema_info(self.h, ctypes.byref(d), ctypes.byref(u), ctypes.byref(on)),
+                 "get_ema_info")
+        return float(d.value), int(u.value), bool(on.value)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with m.ema_weights(): m.evaluate(...)`: inside, forward / evaluate / logits run on the averaged
+        weights and params() returns them; training calls raise.  The live weights are back on exit,
+        however the block ends (vit_trainer_ema_weights)."""
+        self._ok(lib().vit_trainer_ema_weights(self.h, 1), "ema_weights")
+        try:
+            yield self
+        finally:
+            self._ok(lib().vit_trainer_ema_weights(self.h, 0), "ema_weights")
 
     def adamw_state(self):
         """(m, v, t) in canonical order."""

@@ -114,7 +114,7 @@ int vit_checkpoint_read_info(const char* path, vit_checkpoint_info_t* info) {
         set_error("checkpoint %s: seek failed", path);
         return 1;
     }
-    const long long want = VIT_CKPT_HEADER_BYTES + in.num_params * 4 * (in.has_opt ? 3 : 1);
+    const long long want = VIT_CKPT_HEADER_BYTES + in.num_params * 4 * ((in.has_opt ? 3 : 1) + ((h[10] & 2) ? 1 : 0));
     const long long have = (long long)ftello(fh.f);
     if (have != want) {
         set_error("checkpoint %s: %lld bytes, expected %lld", path, have, want);
@@ -126,7 +126,13 @@ int vit_checkpoint_read_info(const char* path, vit_checkpoint_info_t* info) {
 
 int vit_checkpoint_write(const char* path, const vit_config_t* cfg, const float* params,
                          const float* m, const float* v, int step, const vit_adamw_t* adamw) {
-    if (!path || !cfg || !params || (!m) != (!v)) {
+    return vit_checkpoint_write_ex(path, cfg, params, m, v, step, adamw, nullptr, 0.f, 0);
+}
+
+int vit_checkpoint_write_ex(const char* path, const vit_config_t* cfg, const float* params,
+                            const float* m, const float* v, int step, const vit_adamw_t* adamw,
+                            const float* ema, float ema_decay, long long ema_updates) {
+    if (!path || !cfg || !params || (!m) != (!v) || (ema && ema_updates < 0)) {
         set_error("vit_checkpoint_write: bad arguments");
         return 1;
     }
@@ -147,7 +153,7 @@ int vit_checkpoint_write(const char* path, const vit_config_t* cfg, const float*
     hdr[7] = cfg->img;
     hdr[8] = cfg->patch;
     hdr[9] = cfg->in_ch;
-    hdr[10] = m ? 1 : 0;
+    hdr[10] = (m ? 1 : 0) | (ema ? 2 : 0);
     hdr[11] = m ? step : 0;
     hdr[12] = (int32_t)(uint32_t)(n & 0xffffffffLL);
     hdr[13] = (int32_t)(uint32_t)(n >> 32);
@@ -156,6 +162,11 @@ int vit_checkpoint_write(const char* path, const vit_config_t* cfg, const float*
         hdr[15] = (int32_t)fbits(adamw->beta2);
         hdr[16] = (int32_t)fbits(adamw->eps);
         hdr[17] = (int32_t)fbits(adamw->weight_decay);
+    }
+    if (ema) {
+        hdr[18] = (int32_t)fbits(ema_decay);
+        hdr[19] = (int32_t)(uint32_t)(ema_updates & 0xffffffffLL);
+        hdr[20] = (int32_t)(uint32_t)(ema_updates >> 32);
     }
     // write to path.tmp and rename, so an interrupted save never leaves a truncated checkpoint
     const std::string tmp = std::string(path) + ".tmp";
@@ -168,6 +179,7 @@ int vit_checkpoint_write(const char* path, const vit_config_t* cfg, const float*
         bool ok = write_all(fh.f, hdr.data(), VIT_CKPT_HEADER_BYTES) &&
                   write_all(fh.f, params, (size_t)n * 4);
         if (ok && m) ok = write_all(fh.f, m, (size_t)n * 4) && write_all(fh.f, v, (size_t)n * 4);
+        if (ok && ema) ok = write_all(fh.f, ema, (size_t)n * 4);
         // durable before the rename: the data blocks must reach the disk before the new name does
         ok = ok && fflush(fh.f) == 0 && fsync(fileno(fh.f)) == 0;
         if (!ok) {
@@ -215,6 +227,34 @@ int vit_checkpoint_read(const char* path, const vit_config_t* cfg, float* params
         if (ok && v) ok = read_all(fh.f, v, (size_t)in.num_params * 4);
         if (!ok) {
             set_error("checkpoint %s: short optimizer section", path);
+            return 1;
+        }
+    }
+    return 0;
+}
+
+int vit_checkpoint_read_ema(const char* path, const vit_config_t* cfg, float* ema, float* decay,
+                            long long* updates, int* has_ema) {
+    vit_checkpoint_info_t in;
+    if (vit_checkpoint_read_info(path, &in)) return 1;  // (validates the size of either layout)
+    if (!cfg || memcmp(&in.cfg, cfg, sizeof(vit_config_t)) != 0) {
+        set_error("checkpoint %s: config differs from the model's", path);
+        return 1;
+    }
+    int32_t h[21];
+    File fh(fopen(path, "rb"));
+    if (!fh.f || !read_all(fh.f, h, sizeof(h))) {
+        set_error("checkpoint %s: short header", path);
+        return 1;
+    }
+    const bool has = (h[10] & 2) != 0;
+    if (has_ema) *has_ema = has ? 1 : 0;
+    if (decay) *decay = has ? bitsf((uint32_t)h[18]) : 0.f;
+    if (updates) *updates = has ? (long long)(uint32_t)h[19] | ((long long)(uint32_t)h[20] << 32) : 0;
+    if (has && ema) {
+        const long long skip = VIT_CKPT_HEADER_BYTES + in.num_params * 4 * (in.has_opt ? 3 : 1);
+        if (fseeko(fh.f, skip, SEEK_SET) != 0 || !read_all(fh.f, ema, (size_t)in.num_params * 4)) {
+            set_error("checkpoint %s: short EMA section", path);
             return 1;
         }
     }

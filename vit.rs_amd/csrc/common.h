@@ -173,6 +173,25 @@ __device__ __forceinline__ float clip_scale(float c, float g) {
     return c * g;
 }
 
+// Exponential moving average of the weights: e' = fl32(fl32(d * e) + fl32(omd * p)) with p the
+// fp32 master value the optimizer has just written and omd = (float)(1.0 - (double)d) taken once on the
+// host: numpy's fp32 `d * e + omd * p`, each product and the sum rounded on its own (no contraction).
+// The fused optimizer kernels (EMA = true instantiations) and the stand-alone ema_update share these.
+struct EmaArg {
+    float* e;      // the average's arena, the layout of p
+    float d, omd;
+};
+__device__ __forceinline__ float ema_blend(float e, float p, float d, float omd) {
+#pragma clang fp contract(off)
+    const float a = d * e;
+    const float b = omd * p;
+    return a + b;
+}
+__device__ __forceinline__ void ema_blend4(float4& ev, const float4& pv, float d, float omd) {
+    ev.x = ema_blend(ev.x, pv.x, d, omd); ev.y = ema_blend(ev.y, pv.y, d, omd);
+    ev.z = ema_blend(ev.z, pv.z, d, omd); ev.w = ema_blend(ev.w, pv.w, d, omd);
+}
+
 // AdamW (oracle ref_adamw_step): one element, every operation rounded like the
 // oracle's line-by-line C (no contraction, correctly rounded sqrt / divide).  omb1 = 1-beta1, omb2 = 1-beta2,
 // bc1/bc2 = the bias corrections 1 - beta^t, computed on the host exactly as the oracle does.
@@ -252,20 +271,23 @@ __device__ __forceinline__ void adamw_update4(float4& pv, float4 gv, float4& mv,
 }
 // One tile of the grouped SGD: n4 float4s from element beg (a multiple of 64), hyper-parameters
 // uniform over the tile.  A full tile issues its GROUP_UNROLL loads per array before the first use.
-// SHADOW: also pbf = bf16(p), as the ungrouped bf16 kernel.
-template <bool CLIP, bool SHADOW>
+// SHADOW: also pbf = bf16(p), as the ungrouped bf16 kernel.  EMA: also em.e = ema_blend(em.e, p') (the
+// EMA = false instantiations are the code as it was).
+template <bool CLIP, bool SHADOW, bool EMA = false>
 __device__ __forceinline__ void sgd_group_tile(float* __restrict__ p, bf16_t* __restrict__ pbf,
                                                const float* __restrict__ g, long long beg, int n4, float lr,
-                                               float c) {
+                                               float c, EmaArg em = EmaArg{nullptr, 0.f, 0.f}) {
     float4* __restrict__ p4 = reinterpret_cast<float4*>(p + beg);
     const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + beg);
     uint2* __restrict__ b2 = SHADOW ? reinterpret_cast<uint2*>(pbf + beg) : nullptr;
+    float4* __restrict__ e4 = EMA ? reinterpret_cast<float4*>(em.e + beg) : nullptr;
     if (n4 == GROUP_TILE4) {
-        float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL];
+        float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL], ev[GROUP_UNROLL];
 #pragma unroll
         for (int k = 0; k < GROUP_UNROLL; k++) {
             pv[k] = p4[threadIdx.x + k * GROUP_THREADS];
             gv[k] = g4[threadIdx.x + k * GROUP_THREADS];
+            if (EMA) ev[k] = e4[threadIdx.x + k * GROUP_THREADS];
         }
 #pragma unroll
         for (int k = 0; k < GROUP_UNROLL; k++) {
@@ -273,6 +295,10 @@ __device__ __forceinline__ void sgd_group_tile(float* __restrict__ p, bf16_t* __
             sgd_update4<CLIP>(pv[k], gv[k], lr, c);
             p4[i] = pv[k];
             if (SHADOW) b2[i] = make_uint2(pack_bf16x2(pv[k].x, pv[k].y), pack_bf16x2(pv[k].z, pv[k].w));
+            if (EMA) {
+                ema_blend4(ev[k], pv[k], em.d, em.omd);
+                e4[i] = ev[k];
+            }
         }
     } else {
         for (int i = threadIdx.x; i < n4; i += GROUP_THREADS) {
@@ -280,6 +306,11 @@ __device__ __forceinline__ void sgd_group_tile(float* __restrict__ p, bf16_t* __
             sgd_update4<CLIP>(pv, g4[i], lr, c);
             p4[i] = pv;
             if (SHADOW) b2[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
+            if (EMA) {
+                float4 ev = e4[i];
+                ema_blend4(ev, pv, em.d, em.omd);
+                e4[i] = ev;
+            }
         }
     }
 }

@@ -74,6 +74,21 @@ __global__ __launch_bounds__(GROUP_THREADS) void sgd_groups_k(float* __restrict_
         sgd_group_tile<CLIP, false>(p, nullptr, g, beg, n4, group_hp(lr, gt.lr_mul[seg]), c);
     }
 }
+// e = ema_blend(e, p) (common.h): n4 float4s, then the elements [4 n4, n) as scalars.
+// 12 B of HBM traffic per element; the trainer's bf16 / fp8 optimizer kernels fuse the same statement
+// on the value they hold in registers (8 B)
+__global__ void ema_update_k(float* __restrict__ e, const float* __restrict__ p, long long n4, long long n, float d,
+                             float omd) {
+    const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long nth = (long long)gridDim.x * blockDim.x;
+    for (long long i = tid; i < n4; i += nth) {
+        float4 ev = reinterpret_cast<float4*>(e)[i];
+        const float4 pv = reinterpret_cast<const float4*>(p)[i];
+        ema_blend4(ev, pv, d, omd);
+        reinterpret_cast<float4*>(e)[i] = ev;
+    }
+    for (long long i = n4 * 4 + tid; i < n; i += nth) e[i] = ema_blend(e[i], p[i], d, omd);
+}
 
 // ------------------------------------------------------------------ sum of squares (gradient norm)
 // slots[blockIdx.x] = sum of x[i]^2 over this workgroup's grid-stride share of x[0..n): every element
@@ -982,6 +997,14 @@ void sgd_clip(float* p, const float* g, long long n, float lr, const ClipRec* re
     sgd_clip_k<<<grid_for(n, 256), 256, 0, s>>>(p, g, n, lr, rec);
     after_launch("sgd_step_clipped");
 }
+void ema_update_on(float* e, const float* p, long long n, float d, float omd, hipStream_t s) {
+    if (n <= 0) return;
+    const bool vec = (((uintptr_t)e | (uintptr_t)p) & 15) == 0;
+    const long long n4 = vec ? n / 4 : 0;
+    ema_update_k<<<grid_for(vec ? (n + 3) / 4 : n, 256), 256, 0, s>>>(e, p, n4, n, d, omd);
+    after_launch("ema_update");
+    count_hit(VIT_HIT_EMA);
+}
 int group_grid(int ntiles) { return ntiles < 2048 ? ntiles : 2048; }
 void sgd_groups(float* p, const float* g, const GroupTab& gt, int tile_begin, int ntiles, float lr,
                 const ClipRec* rec, hipStream_t s) {
@@ -1287,6 +1310,11 @@ void patch_embed_backward(float* dpatch_w, float* dpatch_b, float* dcls, float* 
 }
 void sgd_step(float* params, const float* grads, long long n, float lr) {
     sgd(params, grads, n, lr, stream());
+}
+void ema_update(float* ema, const float* params, long long n, float decay) {
+    VIT_REQUIRE(n >= 0 && decay >= 0.f && decay <= 1.f, "ema_update: n %lld, decay %g of [0, 1]", n, (double)decay);
+    VIT_REQUIRE(n == 0 || (ema && params), "ema_update: null pointer");
+    ema_update_on(ema, params, n, decay, (float)(1.0 - (double)decay), stream());
 }
 void grad_sumsq(double* out, const float* x, long long n) {
     VIT_REQUIRE(n >= 0, "grad_sumsq: n %lld", n);

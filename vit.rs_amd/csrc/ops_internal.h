@@ -44,6 +44,8 @@ void sgd_clip(float* p, const float* g, long long n, float lr, const ClipRec* re
 // of the whole arena p / g with lr * lr_mul[segment]; rec nullable = no clipping.  group_grid = the
 // workgroups of a grouped optimizer launch over ntiles tiles (8 per CU, the rest grid-strided)
 int group_grid(int ntiles);
+// e = ema_blend(e, p) over n elements on s (the body of ema_update, include/vit_ops.h; common.h ema_blend)
+void ema_update_on(float* e, const float* p, long long n, float d, float omd, hipStream_t s);
 void sgd_groups(float* p, const float* g, const GroupTab& gt, int tile_begin, int ntiles, float lr,
                 const ClipRec* rec, hipStream_t s);
 // sum of squares in double, deterministic (the body of grad_sumsq, include/vit_ops.h):

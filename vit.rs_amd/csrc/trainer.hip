@@ -109,42 +109,59 @@ __global__ void fill_k(float* p, float v, int n) {
 // p -= lr*g; pbf = bf16(p)   (optimizer_step, train_vit.rs:737-743, + bf16 shadow)
 // CLIP: g' = c * g (clip_scale: its own rounding) in place of g; the unclipped instantiation is
 // the kernel as it was
-template <bool CLIP>
+// EMA: also e = ema_blend(e, p') from the value in registers (common.h): one more 16-byte
+// read and write per float4; the EMA = false instantiations are the kernels as they were
+template <bool CLIP, bool EMA>
 __device__ __forceinline__ void sgd_bf16_body(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                                              const float* __restrict__ g, long long n, float lr, float c) {
+                                              const float* __restrict__ g, long long n, float lr, float c,
+                                              EmaArg em) {
     const long long n4 = n / 4;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
          i += (long long)gridDim.x * blockDim.x) {
         float4 pv = reinterpret_cast<float4*>(p)[i];
         float4 gv = reinterpret_cast<const float4*>(g)[i];
+        float4 ev;
+        if (EMA) ev = reinterpret_cast<float4*>(em.e)[i];
         sgd_update4<CLIP>(pv, gv, lr, c);
         reinterpret_cast<float4*>(p)[i] = pv;
         reinterpret_cast<uint2*>(pbf)[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
+        if (EMA) {
+            ema_blend4(ev, pv, em.d, em.omd);
+            reinterpret_cast<float4*>(em.e)[i] = ev;
+        }
     }
     for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
         p[i] = sgd_update(p[i], CLIP ? clip_scale(c, g[i]) : g[i], lr);
         pbf[i] = f2bf(p[i]);
+        if (EMA) em.e[i] = ema_blend(em.e[i], p[i], em.d, em.omd);
     }
 }
+constexpr EmaArg NO_EMA{nullptr, 0.f, 0.f};
 __global__ void sgd_bf16_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
                            const float* __restrict__ g, long long n, float lr) {
-    sgd_bf16_body<false>(p, pbf, g, n, lr, 1.0f);
+    sgd_bf16_body<false, false>(p, pbf, g, n, lr, 1.0f, NO_EMA);
 }
 __global__ void sgd_bf16_clip_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
                                 const float* __restrict__ g, long long n, float lr,
                                 const ClipRec* __restrict__ rec) {
-    sgd_bf16_body<true>(p, pbf, g, n, lr, rec->c);
+    sgd_bf16_body<true, false>(p, pbf, g, n, lr, rec->c, NO_EMA);
+}
+// (rec == nullptr in the unclipped instantiation)
+template <bool CLIP>
+__global__ void sgd_bf16_ema_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
+                               long long n, float lr, const ClipRec* __restrict__ rec, EmaArg em) {
+    sgd_bf16_body<CLIP, true>(p, pbf, g, n, lr, CLIP ? rec->c : 1.0f, em);
 }
 // AdamW over the whole arena (oracle ref_adamw_step), + the bf16 shadow.  One
 // pass: reads p, g, m, v and writes p, m, v (+ pbf) = 7 x 4 B (+2 B) per parameter, HBM-bound.
-// CLIP: as sgd_bf16_body
-template <bool CLIP>
+// CLIP, EMA: as sgd_bf16_body
+template <bool CLIP, bool EMA>
 __device__ __forceinline__ void adamw_body(float* __restrict__ p, bf16_t* __restrict__ pbf,
                                            const float* __restrict__ g, float* __restrict__ m,
                                            float* __restrict__ v, long long n, float lr, float b1, float b2,
                                            float omb1, float omb2, float bc1, float bc2, float eps, float wd,
-                                           float c) {
+                                           float c, EmaArg em) {
     const long long n4 = n / 4;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
          i += (long long)gridDim.x * blockDim.x) {
@@ -152,54 +169,74 @@ __device__ __forceinline__ void adamw_body(float* __restrict__ p, bf16_t* __rest
         float4 gv = reinterpret_cast<const float4*>(g)[i];
         float4 mv = reinterpret_cast<float4*>(m)[i];
         float4 vv = reinterpret_cast<float4*>(v)[i];
+        float4 ev;
+        if (EMA) ev = reinterpret_cast<float4*>(em.e)[i];
         adamw_update4<CLIP>(pv, gv, mv, vv, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, c);
         reinterpret_cast<float4*>(p)[i] = pv;
         reinterpret_cast<float4*>(m)[i] = mv;
         reinterpret_cast<float4*>(v)[i] = vv;
         if (pbf)
             reinterpret_cast<uint2*>(pbf)[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
+        if (EMA) {
+            ema_blend4(ev, pv, em.d, em.omd);
+            reinterpret_cast<float4*>(em.e)[i] = ev;
+        }
     }
     for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
         p[i] = adamw_update(p[i], CLIP ? clip_scale(c, g[i]) : g[i], m[i], v[i], lr, b1, b2, omb1, omb2, bc1,
                             bc2, eps, wd);
         if (pbf) pbf[i] = f2bf(p[i]);
+        if (EMA) em.e[i] = ema_blend(em.e[i], p[i], em.d, em.omd);
     }
 }
 __global__ void adamw_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
                         float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
                         float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd) {
-    adamw_body<false>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, 1.0f);
+    adamw_body<false, false>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, 1.0f, NO_EMA);
 }
 __global__ void adamw_clip_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
                              float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
                              float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd,
                              const ClipRec* __restrict__ rec) {
-    adamw_body<true>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, rec->c);
+    adamw_body<true, false>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, rec->c, NO_EMA);
+}
+template <bool CLIP>
+__global__ void adamw_ema_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
+                            float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
+                            float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd,
+                            const ClipRec* __restrict__ rec, EmaArg em) {
+    adamw_body<CLIP, true>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, CLIP ? rec->c : 1.0f, em);
 }
 // ---- parameter groups (common.h GroupTab): the same updates over the tiles
 // [tile_begin, tile_begin + ntiles) of the whole arena, lr_e = lr * lr_mul and wd_e = wd * wd_mul of
 // the tile's segment (uniform per workgroup iteration).  A gradient chunk is a tile sub-range.
-template <bool CLIP>
+// EM: empty (the kernel as it was, argument list included) or one trailing EmaArg = the EMA instantiation
+__device__ __forceinline__ EmaArg ema_of() { return NO_EMA; }
+__device__ __forceinline__ EmaArg ema_of(EmaArg em) { return em; }
+template <bool CLIP, typename... EM>
 __global__ __launch_bounds__(GROUP_THREADS) void sgd_bf16_groups_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
                                                                    const float* __restrict__ g, GroupTab gt,
                                                                    int tile_begin, int ntiles, float lr,
-                                                                   const ClipRec* __restrict__ rec) {
+                                                                   const ClipRec* __restrict__ rec, EM... ema) {
+    constexpr bool EMA = sizeof...(EM) != 0;
     const float c = CLIP ? rec->c : 1.0f;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         long long beg;
         int n4;
         const int seg = group_tile(gt, tile_begin + t, beg, n4);
-        sgd_group_tile<CLIP, true>(p, pbf, g, beg, n4, group_hp(lr, gt.lr_mul[seg]), c);
+        sgd_group_tile<CLIP, true, EMA>(p, pbf, g, beg, n4, group_hp(lr, gt.lr_mul[seg]), c, ema_of(ema...));
     }
 }
-template <bool CLIP>
+template <bool CLIP, typename... EM>
 __global__ __launch_bounds__(GROUP_THREADS) void adamw_groups_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
                                                                 const float* __restrict__ g, float* __restrict__ m,
                                                                 float* __restrict__ v, GroupTab gt, int tile_begin,
                                                                 int ntiles, float lr, float b1, float b2, float omb1,
                                                                 float omb2, float bc1, float bc2, float eps, float wd,
-                                                                const ClipRec* __restrict__ rec) {
+                                                                const ClipRec* __restrict__ rec, EM... ema) {
+    constexpr bool EMA = sizeof...(EM) != 0;
+    const EmaArg em = ema_of(ema...);
     const float c = CLIP ? rec->c : 1.0f;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         long long beg;
@@ -211,8 +248,9 @@ __global__ __launch_bounds__(GROUP_THREADS) void adamw_groups_k(float* __restric
         float4* __restrict__ m4 = reinterpret_cast<float4*>(m + beg);
         float4* __restrict__ v4 = reinterpret_cast<float4*>(v + beg);
         uint2* __restrict__ s2 = pbf ? reinterpret_cast<uint2*>(pbf + beg) : nullptr;
+        float4* __restrict__ e4 = EMA ? reinterpret_cast<float4*>(em.e + beg) : nullptr;
         if (n4 == GROUP_TILE4) {  // a full tile: every load issued before the first use
-            float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL], mv[GROUP_UNROLL], vv[GROUP_UNROLL];
+            float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL], mv[GROUP_UNROLL], vv[GROUP_UNROLL], ev[GROUP_UNROLL];
 #pragma unroll
             for (int k = 0; k < GROUP_UNROLL; k++) {
                 const int i = threadIdx.x + k * GROUP_THREADS;
@@ -220,6 +258,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void adamw_groups_k(float* __restric
                 gv[k] = g4[i];
                 mv[k] = m4[i];
                 vv[k] = v4[i];
+                if (EMA) ev[k] = e4[i];
             }
 #pragma unroll
             for (int k = 0; k < GROUP_UNROLL; k++) {
@@ -229,6 +268,10 @@ __global__ __launch_bounds__(GROUP_THREADS) void adamw_groups_k(float* __restric
                 m4[i] = mv[k];
                 v4[i] = vv[k];
                 if (s2) s2[i] = make_uint2(pack_bf16x2(pv[k].x, pv[k].y), pack_bf16x2(pv[k].z, pv[k].w));
+                if (EMA) {
+                    ema_blend4(ev[k], pv[k], em.d, em.omd);
+                    e4[i] = ev[k];
+                }
             }
         } else {
             for (int i = threadIdx.x; i < n4; i += GROUP_THREADS) {
@@ -238,6 +281,11 @@ __global__ __launch_bounds__(GROUP_THREADS) void adamw_groups_k(float* __restric
                 m4[i] = mv;
                 v4[i] = vv;
                 if (s2) s2[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
+                if (EMA) {
+                    float4 ev = e4[i];
+                    ema_blend4(ev, pv, em.d, em.omd);
+                    e4[i] = ev;
+                }
             }
         }
     }
@@ -1900,14 +1948,28 @@ struct Trainer {
         }
         if (groups_on) {  // the whole-arena grouped kernel over the chunk's tiles: the same bits
             const int t0 = grp_chunk_tile[c], nt = grp_chunk_tile[c + 1] - t0;
+            if (ema_fuse(false)) {
+                sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s_comm>>>(
+                    params, pbf, grads, grp_tab, t0, nt, early_lr, nullptr, ema_arg());
+                ema_launched("sgd_bf16_groups_ema_chunk");
+                return;
+            }
             sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s_comm>>>(params, pbf, grads, grp_tab, t0, nt,
                                                                                    early_lr, nullptr);
             after_launch("sgd_bf16_groups_chunk");
+            ema_behind(c, s_comm);
             return;
         }
         const long long o = chunk_off[c], n = chunk_off[c + 1] - chunk_off[c];
+        if (ema_fuse(false)) {  // the chunk's range of the average with it: elementwise, the whole-arena pass's bits
+            sgd_bf16_ema_k<false><<<grid_for(n / 4, 256), 256, 0, s_comm>>>(params + o, pbf + o, grads + o, n, early_lr,
+                                                                            nullptr, EmaArg{ema + o, ema_d, ema_omd});
+            ema_launched("sgd_bf16_ema_chunk");
+            return;
+        }
         sgd_bf16_k<<<grid_for(n / 4, 256), 256, 0, s_comm>>>(params + o, pbf + o, grads + o, n, early_lr);
         after_launch("sgd_bf16_chunk");
+        ema_behind(c, s_comm);
     }
     // Global-norm gradient clipping (option of vit_trainer_set_grad_clip).  The sum of
     // squares of the gradients is taken per gradient chunk (the chunk_off ranges, in every mode, so
@@ -2089,6 +2151,87 @@ struct Trainer {
         return true;
     }
 
+    // Exponential moving average of the weights (vit_trainer_set_ema): one fp32 arena in the
+    // layout of params, allocated by the first enabling, advanced by every optimizer step while on: inside the
+    // optimizer kernels (bf16 / fp8 mode, AdamW in every mode), or by ema_update behind the fp32 SGD ops.
+    // ema_view (vit_trainer_ema_weights): the two arena pointers are exchanged, so `params` (and with it
+    // P(), the shadows' source and get_params) is the average and `ema` the live weights; every call
+    // that would train, overwrite or save either is refused until the exchange is undone.
+    float* ema = nullptr;
+    bool ema_on = false, ema_view = false;
+    float ema_d = 0.f, ema_omd = 0.f;
+    long long ema_updates = 0;
+    // option "ema_fused" (default 1): 0 runs the optimizer kernels as they are without EMA and launches
+    // ema_update behind each on the same stream (12 B per parameter instead of 8; the same bits): the A/B of
+    // tools/bench_ema.py.  fp32-mode SGD goes through the ops of ops.hip and always takes that form.
+    bool ema_fused = true;
+    bool ema_fuse(bool adamw) const { return ema_on && ema_fused && (lowp() || adamw); }
+    // the stand-alone update of gradient chunk c (c < 0: the whole arena) behind an un-fused optimizer launch
+    void ema_behind(int c, hipStream_t st) {
+        if (!ema_on) return;
+        const long long o = c < 0 ? 0 : chunk_off[c], n = c < 0 ? arena_elems : chunk_off[c + 1] - chunk_off[c];
+        ema_update_on(ema + o, params + o, n, ema_d, ema_omd, st);
+    }
+    EmaArg ema_arg() const { return EmaArg{ema, ema_d, ema_omd}; }
+    void ema_launched(const char* what) {
+        after_launch(what);
+        count_hit(VIT_HIT_EMA);
+    }
+    // s behind the optimizer work of the side streams (early SGD on s_comm, the side pre-work on s2)
+    void ema_join() {
+        pre_side_wait();
+        VIT_HIP(hipEventRecord(comm_done, s_comm));
+        VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
+    }
+    void ema_set_decay(float d) {
+        ema_d = d;
+        ema_omd = (float)(1.0 - (double)d);
+    }
+    // the average := the current parameters (device copy), count 0
+    bool ema_seed() {
+        if (!ema) ema = alloc<float>(arena_elems);
+        if (!ema) return false;
+        ema_join();
+        VIT_HIP(hipMemcpyAsync(ema, params, (size_t)arena_elems * 4, hipMemcpyDeviceToDevice, s));
+        VIT_HIP(hipStreamSynchronize(s));
+        ema_updates = 0;
+        return !has_error();
+    }
+    bool set_ema(float d) {
+        if (!(d >= 0.f && d < 1.f)) {
+            set_error("vit_trainer_set_ema: decay %g outside [0, 1)", (double)d);
+            return false;
+        }
+        if (d == 0.f) {  // off; the arena stays for the next enabling, which seeds it again
+            ema_on = false;
+            return true;
+        }
+        if (!ema_on && !ema_seed()) return false;
+        ema_set_decay(d);
+        ema_on = true;
+        return true;
+    }
+    bool ema_weights(bool on) {
+        if (on == ema_view || (on && !ema_on)) {
+            set_error(on ? (ema_view ? "vit_trainer_ema_weights: EMA weights already in use"
+                                     : "vit_trainer_ema_weights: EMA is off")
+                         : "vit_trainer_ema_weights: EMA weights not in use");
+            return false;
+        }
+        ema_join();
+        std::swap(params, ema);
+        ema_view = on;
+        refresh_bf16();  // the bf16 shadow, the transposed copies, the padded patch weight, the fp8 MX copies
+        VIT_HIP(hipStreamSynchronize(s));
+        return !has_error();
+    }
+    // false (with the error set) while the averaged weights are exchanged in
+    bool ema_unlocked(const char* who) {
+        if (!ema_view) return true;
+        set_error("%s: EMA weights in use", who);
+        return false;
+    }
+
     bool ensure_adam() {
         if (adam_m) return true;
         adam_m = alloc<float>(arena_elems);
@@ -2194,11 +2337,14 @@ struct Trainer {
         if (!ensure_adam()) return;
         adam_t += 1;
         adam_hp = hp;
+        if (ema_on) ema_updates++;
         // bias corrections and 1-beta exactly as the oracle rounds them (pow in double -> fp32)
         const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)adam_t);
         const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)adam_t);
         tbeg(TC_SGD, 0);
-        if (groups_on) {  // one launch over every tile of the arena
+        if (ema_fuse(true)) {
+            adamw_ema(lr, hp, bc1, bc2);
+        } else if (groups_on) {  // one launch over every tile of the arena
             const int nt = grp_chunk_tile[n_chunks];
             bf16_t* shadow = lowp() ? pbf : nullptr;
             if (clip_on()) {
@@ -2225,12 +2371,73 @@ struct Trainer {
                 hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay);
             after_launch("adamw");
         }
+        if (!ema_fuse(true)) ema_behind(-1, s);
         tend();
         if (lowp()) refresh_transposed();
     }
 
+    // the AdamW launches with the average fused (ema_on): the same grids, the EMA instantiations
+    void adamw_ema(float lr, const vit_adamw_t& hp, float bc1, float bc2) {
+        bf16_t* shadow = lowp() ? pbf : nullptr;
+        const ClipRec* rec = nullptr;
+        if (clip_on()) {
+            clip_norm();
+            rec = clip_rec;
+        }
+        const float omb1 = 1.0f - hp.beta1, omb2 = 1.0f - hp.beta2;
+        if (groups_on) {
+            const int nt = grp_chunk_tile[n_chunks];
+            if (rec)
+                adamw_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
+                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, omb1, omb2, bc1, bc2,
+                    hp.eps, hp.weight_decay, rec, ema_arg());
+            else
+                adamw_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
+                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, omb1, omb2, bc1, bc2,
+                    hp.eps, hp.weight_decay, nullptr, ema_arg());
+            ema_launched(rec ? "adamw_groups_ema_clipped" : "adamw_groups_ema");
+        } else {
+            const int grid = grid_for(arena_elems / 4, 256);
+            if (rec)
+                adamw_ema_k<true><<<grid, 256, 0, s>>>(params, shadow, grads, adam_m, adam_v, arena_elems, lr, hp.beta1,
+                                                       hp.beta2, omb1, omb2, bc1, bc2, hp.eps, hp.weight_decay, rec,
+                                                       ema_arg());
+            else
+                adamw_ema_k<false><<<grid, 256, 0, s>>>(params, shadow, grads, adam_m, adam_v, arena_elems, lr, hp.beta1,
+                                                        hp.beta2, omb1, omb2, bc1, bc2, hp.eps, hp.weight_decay, nullptr,
+                                                        ema_arg());
+            ema_launched(rec ? "adamw_ema_clipped" : "adamw_ema");
+        }
+    }
+    // the bf16 / fp8 SGD launches with the average fused
+    void sgd_ema(float lr) {
+        const ClipRec* rec = nullptr;
+        if (clip_on()) {
+            clip_norm();
+            rec = clip_rec;
+        }
+        if (groups_on) {
+            const int nt = grp_chunk_tile[n_chunks];
+            if (rec)
+                sgd_bf16_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt,
+                                                                                     lr, rec, ema_arg());
+            else
+                sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt,
+                                                                                      lr, nullptr, ema_arg());
+            ema_launched(rec ? "sgd_bf16_groups_ema_clipped" : "sgd_bf16_groups_ema");
+        } else {
+            const int grid = grid_for(arena_elems / 4, 256);
+            if (rec)
+                sgd_bf16_ema_k<true><<<grid, 256, 0, s>>>(params, pbf, grads, arena_elems, lr, rec, ema_arg());
+            else
+                sgd_bf16_ema_k<false><<<grid, 256, 0, s>>>(params, pbf, grads, arena_elems, lr, nullptr, ema_arg());
+            ema_launched(rec ? "sgd_bf16_ema_clipped" : "sgd_bf16_ema");
+        }
+    }
+
     void step(float lr) {
         pre_side_wait();
+        if (ema_on) ema_updates++;
         if (early_done) {  // every chunk already updated on s_comm (train_step with early SGD)
             early_done = false;
             VIT_HIP(hipEventRecord(comm_done, s_comm));
@@ -2240,7 +2447,9 @@ struct Trainer {
         }
         finish_allreduce();
         tbeg(TC_SGD, 0);
-        if (groups_on) {  // one launch over every tile of the arena
+        if (ema_fuse(false)) {
+            sgd_ema(lr);
+        } else if (groups_on) {  // one launch over every tile of the arena
             const int nt = grp_chunk_tile[n_chunks];
             const ClipRec* rec = nullptr;
             if (clip_on()) {
@@ -2272,6 +2481,7 @@ struct Trainer {
         } else {
             sgd(params, grads, arena_elems, lr, s);
         }
+        if (!ema_fuse(false)) ema_behind(-1, s);
         tend();
         if (lowp()) refresh_transposed();
     }
@@ -2363,6 +2573,7 @@ void vit_trainer_destroy(vit_trainer_t* h) {
 long long vit_trainer_num_params(const vit_trainer_t* h) { return h->t.n_params; }
 long long vit_trainer_device_bytes(const vit_trainer_t* h) { return (long long)h->t.dev_bytes; }
 int vit_trainer_set_params(vit_trainer_t* h, const float* hp) {
+    if (!h->t.ema_unlocked("vit_trainer_set_params")) return 1;
     h->t.canon_to_device(hp, h->t.params);
     h->t.refresh_bf16();
     VIT_HIP(hipStreamSynchronize(h->t.s));
@@ -2516,6 +2727,7 @@ int vit_trainer_get_drop_path(vit_trainer_t* h, float* out, int* used) {
 }
 int vit_trainer_zero_grad(vit_trainer_t* h) {
     auto& t = h->t;
+    if (!t.ema_unlocked("vit_trainer_zero_grad")) return 1;
     t.clip_parts_valid = false;
     // the previous step's all-reduce must be done with the arena before it is cleared
     if (t.comm) {
@@ -2533,6 +2745,7 @@ int vit_trainer_zero_grad(vit_trainer_t* h) {
 }
 int vit_trainer_backward(vit_trainer_t* h) {
     auto& t = h->t;
+    if (!t.ema_unlocked("vit_trainer_backward")) return 1;
     if (!t.has_targets) {
         set_error("vit_trainer_backward: the batch has no targets (forward-only batch)");
         return 1;
@@ -2545,11 +2758,13 @@ int vit_trainer_backward(vit_trainer_t* h) {
     return vit::has_error();
 }
 int vit_trainer_step(vit_trainer_t* h, float lr) {
+    if (!h->t.ema_unlocked("vit_trainer_step")) return 1;
     h->t.step(lr);
     return vit::has_error();
 }
 int vit_trainer_train_step(vit_trainer_t* h, float lr, int b_global) {
     auto& t = h->t;
+    if (!t.ema_unlocked("vit_trainer_train_step")) return 1;
     vit_trainer_zero_grad(h);
     vit_trainer_forward(h, b_global);
     // the fused step knows lr before the backward: SGD per finished chunk (Trainer::early_sgd)
@@ -2589,6 +2804,7 @@ int vit_trainer_set_augment_plan(vit_trainer_t* h, const vit_aug_op_t* host_plan
 }
 int vit_trainer_step_adamw(vit_trainer_t* h, float lr, float beta1, float beta2, float eps,
                            float weight_decay) {
+    if (!h->t.ema_unlocked("vit_trainer_step_adamw")) return 1;
     h->t.step_adamw(lr, vit_adamw_t{beta1, beta2, eps, weight_decay});
     return vit::has_error();
 }
@@ -2632,6 +2848,53 @@ int vit_trainer_get_param_groups(vit_trainer_t* h, float* lr_mul, float* wd_mul,
     if (on) *on = t.groups_on ? 1 : 0;
     return 0;
 }
+int vit_trainer_set_ema(vit_trainer_t* h, float decay) {
+    if (!h) {
+        set_error("vit_trainer_set_ema: null trainer");
+        return 1;
+    }
+    if (!h->t.ema_unlocked("vit_trainer_set_ema")) return 1;
+    return h->t.set_ema(decay) ? 0 : 1;
+}
+int vit_trainer_get_ema_info(vit_trainer_t* h, float* decay, long long* updates, int* on) {
+    if (!h) {
+        set_error("vit_trainer_get_ema_info: null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    if (decay) *decay = t.ema_on ? t.ema_d : 0.f;
+    if (updates) *updates = t.ema_updates;
+    if (on) *on = t.ema_on ? 1 : 0;
+    return 0;
+}
+int vit_trainer_get_ema(vit_trainer_t* h, float* host) {
+    if (!h || !host || !h->t.ema_on) {
+        set_error("vit_trainer_get_ema: %s", !h || !host ? "null argument" : "EMA is off");
+        return 1;
+    }
+    auto& t = h->t;
+    t.ema_join();
+    t.device_to_canon(t.ema_view ? t.params : t.ema, host);  // (exchanged in: `params` is the average)
+    return vit::has_error();
+}
+int vit_trainer_set_ema_params(vit_trainer_t* h, const float* host) {
+    if (!h || !host || !h->t.ema_on) {
+        set_error("vit_trainer_set_ema_params: %s", !h || !host ? "null argument" : "EMA is off");
+        return 1;
+    }
+    auto& t = h->t;
+    if (!t.ema_unlocked("vit_trainer_set_ema_params")) return 1;
+    t.ema_join();
+    t.canon_to_device(host, t.ema);
+    return vit::has_error();
+}
+int vit_trainer_ema_weights(vit_trainer_t* h, int on) {
+    if (!h) {
+        set_error("vit_trainer_ema_weights: null trainer");
+        return 1;
+    }
+    return h->t.ema_weights(on != 0) ? 0 : 1;
+}
 int vit_trainer_get_adamw_state(vit_trainer_t* h, float* m, float* v, int* step) {
     auto& t = h->t;
     if (step) *step = t.adam_t;
@@ -2664,10 +2927,25 @@ int vit_trainer_eval(vit_trainer_t* h, int* host_pred, int* host_correct) {
 }
 int vit_trainer_save_checkpoint(vit_trainer_t* h, const char* path) {
     auto& t = h->t;
+    if (!t.ema_unlocked("vit_trainer_save_checkpoint")) return 1;
     VIT_HIP(hipDeviceSynchronize());
     if (vit::has_error()) return 1;
     std::vector<float> p((size_t)t.n_params), m, v;
     t.device_to_canon(t.params, p.data());
+    if (t.ema_on) {  // (a trainer with EMA off writes the file through the call it always used)
+        std::vector<float> e((size_t)t.n_params);
+        t.device_to_canon(t.ema, e.data());
+        if (t.adam_m) {
+            m.resize((size_t)t.n_params);
+            v.resize((size_t)t.n_params);
+            t.device_to_canon(t.adam_m, m.data());
+            t.device_to_canon(t.adam_v, v.data());
+        }
+        if (vit::has_error()) return 1;
+        return vit_checkpoint_write_ex(path, &t.cfg, p.data(), t.adam_m ? m.data() : nullptr,
+                                       t.adam_m ? v.data() : nullptr, t.adam_t, &t.adam_hp, e.data(), t.ema_d,
+                                       t.ema_updates);
+    }
     if (t.adam_m) {
         m.resize((size_t)t.n_params);
         v.resize((size_t)t.n_params);
@@ -2680,9 +2958,22 @@ int vit_trainer_save_checkpoint(vit_trainer_t* h, const char* path) {
 }
 int vit_trainer_load_checkpoint(vit_trainer_t* h, const char* path) {
     auto& t = h->t;
+    if (!t.ema_unlocked("vit_trainer_load_checkpoint")) return 1;
     vit_checkpoint_info_t info;
     if (vit_checkpoint_read_info(path, &info)) return 1;
-    std::vector<float> p((size_t)t.n_params), m, v;
+    std::vector<float> p((size_t)t.n_params), m, v, e;
+    float e_decay = 0.f;
+    long long e_updates = 0;
+    int has_ema = 0;
+    if (vit_checkpoint_read_ema(path, &t.cfg, nullptr, &e_decay, &e_updates, &has_ema)) return 1;
+    if (has_ema) {
+        if (!(e_decay > 0.f && e_decay < 1.f)) {
+            set_error("checkpoint %s: EMA decay %g outside (0, 1)", path, (double)e_decay);
+            return 1;
+        }
+        e.resize((size_t)t.n_params);
+        if (vit_checkpoint_read_ema(path, &t.cfg, e.data(), nullptr, nullptr, nullptr)) return 1;
+    }
     if (info.has_opt) {
         m.resize((size_t)t.n_params);
         v.resize((size_t)t.n_params);
@@ -2703,6 +2994,15 @@ int vit_trainer_load_checkpoint(vit_trainer_t* h, const char* path) {
         VIT_HIP(hipMemsetAsync(t.adam_m, 0, t.arena_elems * 4, t.s));
         VIT_HIP(hipMemsetAsync(t.adam_v, 0, t.arena_elems * 4, t.s));
         t.adam_t = 0;
+    }
+    if (has_ema) {  // the file's average, decay and count; EMA on
+        if (!t.ema && !(t.ema = t.alloc<float>(t.arena_elems))) return 1;
+        t.canon_to_device(e.data(), t.ema);
+        t.ema_set_decay(e_decay);
+        t.ema_updates = e_updates;
+        t.ema_on = true;
+    } else if (t.ema_on) {  // a file without one restarts the average from the loaded parameters
+        if (!t.ema_seed()) return 1;
     }
     VIT_HIP(hipStreamSynchronize(t.s));
     return vit::has_error();
@@ -2824,6 +3124,8 @@ int vit_trainer_set_option(vit_trainer_t* h, const char* name, int value) {
         t.ln_mx = value != 0;
     } else if (n == "fp8_ln_leftover") {  // fp8: LayerNorm -> MX forward, last partial round as rows (default 0)
         t.ln_left = value != 0;
+    } else if (n == "ema_fused") {  // 0: EMA as ema_update launches behind the un-fused optimizer kernels (A/B)
+        t.ema_fused = value != 0;
     } else if (n == "early_sgd") {  // one GPU: SGD per finished gradient chunk inside train_step (default: fp8 mode only)
         t.early_sgd = value < 0 ? -1 : value != 0;
     } else if (n == "pre_side") {  // bf16 / fp8: gradient clear + transposed weights on s2 beside the forward (default 1)
