@@ -1,4 +1,5 @@
-"""Concurrency analysis of a rocprofv3 kernel trace: for the last N steps (split at sgd_bf16_k),
+"""Concurrency analysis of a rocprofv3 kernel trace: for the last N steps (split at the bf16 SGD
+step kernel, sgd_flat_k<false, true, false> of optimizer.hip),
 the wall span, the union of busy intervals, and per-stream / per-kernel busy time.
     python tools/timeline.py gpurun_out/tl/run_results.db|run_kernel_trace.csv [steps]"""
 import sqlite3
@@ -14,7 +15,7 @@ if db.endswith(".csv"):  # rocprofv3 --output-format csv kernel trace
 else:
     c = sqlite3.connect(db)
     rows = c.execute("select name, stream_id, start, end from kernels order by start").fetchall()
-sgd = [i for i, r in enumerate(rows) if "sgd_bf16_k" in r[0]]
+sgd = [i for i, r in enumerate(rows) if "sgd_flat_k<false,true,false>" in r[0].replace(" ", "")]
 lo, hi = sgd[-nsteps - 1] + 1, sgd[-1] + 1
 seg = rows[lo:hi]
 t0, t1 = seg[0][2], max(r[3] for r in seg)

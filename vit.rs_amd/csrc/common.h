@@ -269,51 +269,6 @@ __device__ __forceinline__ void adamw_update4(float4& pv, float4 gv, float4& mv,
     pv.z = adamw_update(pv.z, gv.z, mv.z, vv.z, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
     pv.w = adamw_update(pv.w, gv.w, mv.w, vv.w, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
 }
-// One tile of the grouped SGD: n4 float4s from element beg (a multiple of 64), hyper-parameters
-// uniform over the tile.  A full tile issues its GROUP_UNROLL loads per array before the first use.
-// SHADOW: also pbf = bf16(p), as the ungrouped bf16 kernel.  EMA: also em.e = ema_blend(em.e, p') (the
-// EMA = false instantiations are the code as it was).
-template <bool CLIP, bool SHADOW, bool EMA = false>
-__device__ __forceinline__ void sgd_group_tile(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                                               const float* __restrict__ g, long long beg, int n4, float lr,
-                                               float c, EmaArg em = EmaArg{nullptr, 0.f, 0.f}) {
-    float4* __restrict__ p4 = reinterpret_cast<float4*>(p + beg);
-    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + beg);
-    uint2* __restrict__ b2 = SHADOW ? reinterpret_cast<uint2*>(pbf + beg) : nullptr;
-    float4* __restrict__ e4 = EMA ? reinterpret_cast<float4*>(em.e + beg) : nullptr;
-    if (n4 == GROUP_TILE4) {
-        float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL], ev[GROUP_UNROLL];
-#pragma unroll
-        for (int k = 0; k < GROUP_UNROLL; k++) {
-            pv[k] = p4[threadIdx.x + k * GROUP_THREADS];
-            gv[k] = g4[threadIdx.x + k * GROUP_THREADS];
-            if (EMA) ev[k] = e4[threadIdx.x + k * GROUP_THREADS];
-        }
-#pragma unroll
-        for (int k = 0; k < GROUP_UNROLL; k++) {
-            const int i = threadIdx.x + k * GROUP_THREADS;
-            sgd_update4<CLIP>(pv[k], gv[k], lr, c);
-            p4[i] = pv[k];
-            if (SHADOW) b2[i] = make_uint2(pack_bf16x2(pv[k].x, pv[k].y), pack_bf16x2(pv[k].z, pv[k].w));
-            if (EMA) {
-                ema_blend4(ev[k], pv[k], em.d, em.omd);
-                e4[i] = ev[k];
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < n4; i += GROUP_THREADS) {
-            float4 pv = p4[i];
-            sgd_update4<CLIP>(pv, g4[i], lr, c);
-            p4[i] = pv;
-            if (SHADOW) b2[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
-            if (EMA) {
-                float4 ev = e4[i];
-                ema_blend4(ev, pv, em.d, em.omd);
-                e4[i] = ev;
-            }
-        }
-    }
-}
 
 // XCD-aware bijective remap of a linear workgroup id (cdna_hip_programming.md §5, "XCD swizzle
 // must be bijective"): blocks dealt round-robin over 8 XCDs get contiguous tile ranges per XCD.

@@ -52,28 +52,6 @@ __global__ void sgd_k(float* __restrict__ p, const float* __restrict__ g, long l
          i += (long long)gridDim.x * blockDim.x)
         p[i] = sgd_update(p[i], g[i], lr);
 }
-// the same update on g' = c * g, c read from the clip record (clip_scale, common.h)
-__global__ void sgd_clip_k(float* __restrict__ p, const float* __restrict__ g, long long n, float lr,
-                           const ClipRec* __restrict__ rec) {
-    const float c = rec->c;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x)
-        p[i] = sgd_update(p[i], clip_scale(c, g[i]), lr);
-}
-// the fp32-mode update with parameter groups (common.h GroupTab): workgroups stride over the tiles
-// [tile_begin, tile_begin + ntiles) of the whole arena p / g, lr_e = lr * lr_mul[segment] per tile
-template <bool CLIP>
-__global__ __launch_bounds__(GROUP_THREADS) void sgd_groups_k(float* __restrict__ p, const float* __restrict__ g,
-                                                              GroupTab gt, int tile_begin, int ntiles, float lr,
-                                                              const ClipRec* __restrict__ rec) {
-    const float c = CLIP ? rec->c : 1.0f;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        long long beg;
-        int n4;
-        const int seg = group_tile(gt, tile_begin + t, beg, n4);
-        sgd_group_tile<CLIP, false>(p, nullptr, g, beg, n4, group_hp(lr, gt.lr_mul[seg]), c);
-    }
-}
 // e = ema_blend(e, p) (common.h): n4 float4s, then the elements [4 n4, n) as scalars.
 // 12 B of HBM traffic per element; the trainer's bf16 / fp8 optimizer kernels fuse the same statement
 // on the value they hold in registers (8 B)
@@ -987,16 +965,6 @@ void convert_f2bf(bf16_t* out, const float* inp, long long n, hipStream_t s) {
     f2bf_k<<<grid_for(n, 256), 256, 0, s>>>(out, inp, n);
     after_launch("convert_f32_to_bf16");
 }
-void sgd(float* p, const float* g, long long n, float lr, hipStream_t s) {
-    if (n <= 0) return;
-    sgd_k<<<grid_for(n, 256), 256, 0, s>>>(p, g, n, lr);
-    after_launch("sgd_step");
-}
-void sgd_clip(float* p, const float* g, long long n, float lr, const ClipRec* rec, hipStream_t s) {
-    if (n <= 0) return;
-    sgd_clip_k<<<grid_for(n, 256), 256, 0, s>>>(p, g, n, lr, rec);
-    after_launch("sgd_step_clipped");
-}
 void ema_update_on(float* e, const float* p, long long n, float d, float omd, hipStream_t s) {
     if (n <= 0) return;
     const bool vec = (((uintptr_t)e | (uintptr_t)p) & 15) == 0;
@@ -1004,16 +972,6 @@ void ema_update_on(float* e, const float* p, long long n, float d, float omd, hi
     ema_update_k<<<grid_for(vec ? (n + 3) / 4 : n, 256), 256, 0, s>>>(e, p, n4, n, d, omd);
     after_launch("ema_update");
     count_hit(VIT_HIT_EMA);
-}
-int group_grid(int ntiles) { return ntiles < 2048 ? ntiles : 2048; }
-void sgd_groups(float* p, const float* g, const GroupTab& gt, int tile_begin, int ntiles, float lr,
-                const ClipRec* rec, hipStream_t s) {
-    if (ntiles <= 0) return;
-    if (rec)
-        sgd_groups_k<true><<<group_grid(ntiles), GROUP_THREADS, 0, s>>>(p, g, gt, tile_begin, ntiles, lr, rec);
-    else
-        sgd_groups_k<false><<<group_grid(ntiles), GROUP_THREADS, 0, s>>>(p, g, gt, tile_begin, ntiles, lr, nullptr);
-    after_launch(rec ? "sgd_step_groups_clipped" : "sgd_step_groups");
 }
 // a function of n alone (not of the device or of anything scheduling-dependent): one workgroup per
 // 4096 elements (four 16-byte loads per thread), at most 1024
@@ -1308,8 +1266,11 @@ void patch_embed_backward(float* dpatch_w, float* dpatch_b, float* dcls, float* 
     gemm_f32(a, s);
     patch_small_grads(dcls, dwpe, dpatch_b, dencoded, B, T, C, s, ws + o_t);
 }
+// (any n and any alignment: the scalar kernel; the trainer's own steps are optimizer.hip)
 void sgd_step(float* params, const float* grads, long long n, float lr) {
-    sgd(params, grads, n, lr, stream());
+    if (n <= 0) return;
+    sgd_k<<<grid_for(n, 256), 256, 0, stream()>>>(params, grads, n, lr);
+    after_launch("sgd_step");
 }
 void ema_update(float* ema, const float* params, long long n, float decay) {
     VIT_REQUIRE(n >= 0 && decay >= 0.f && decay <= 1.f, "ema_update: n %lld, decay %g of [0, 1]", n, (double)decay);

@@ -37,17 +37,8 @@ void ln_backward_bf16_stream_dp(bf16_t* dres_out, uint8_t* lo_out, bf16_t* dres_
                                 float* part = nullptr);
 int ln_bwd_blocks(long long rows);
 void convert_f2bf(bf16_t* out, const float* inp, long long n, hipStream_t s);
-void sgd(float* p, const float* g, long long n, float lr, hipStream_t s);
-// p -= lr * (rec->c * g), the product c * g rounded on its own (clip_scale)
-void sgd_clip(float* p, const float* g, long long n, float lr, const ClipRec* rec, hipStream_t s);
-// parameter groups (common.h GroupTab): the tiles [tile_begin, tile_begin + ntiles)
-// of the whole arena p / g with lr * lr_mul[segment]; rec nullable = no clipping.  group_grid = the
-// workgroups of a grouped optimizer launch over ntiles tiles (8 per CU, the rest grid-strided)
-int group_grid(int ntiles);
 // e = ema_blend(e, p) over n elements on s (the body of ema_update, include/vit_ops.h; common.h ema_blend)
 void ema_update_on(float* e, const float* p, long long n, float d, float omd, hipStream_t s);
-void sgd_groups(float* p, const float* g, const GroupTab& gt, int tile_begin, int ntiles, float lr,
-                const ClipRec* rec, hipStream_t s);
 // sum of squares in double, deterministic (the body of grad_sumsq, include/vit_ops.h):
 // sumsq_partials writes sumsq_blocks(n) per-workgroup partial sums (a function of n alone; 0 for
 // n <= 0, then nothing is launched) to slots; sumsq_finish / clip_finish sum nslots of them in slot

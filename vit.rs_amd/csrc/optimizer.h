@@ -1,0 +1,35 @@
+// optimizer.h — the optimizer kernels of the trainer behind one parameter block and one launcher
+// (optimizer.hip; the matrix of instantiations is in DESIGN.md §16).
+#pragma once
+#include "common.h"
+
+namespace vit {
+enum OptKind { OPT_SGD, OPT_ADAMW };
+
+struct OptimHp {
+    float lr;
+    float b1, b2, omb1, omb2, bc1, bc2, eps, wd;  // AdamW only (common.h adamw_update)
+};
+// One optimizer launch.  A flat range is the n elements from p / g / ... (n % 4 == 0, 16-byte aligned
+// pointers); a tiled range is the tiles [tile_begin, tile_begin + ntiles) of gt, with p / g / ... the
+// arena bases and lr (AdamW: and wd) multiplied per segment.
+struct OptimArgs {
+    float* p;
+    bf16_t* pbf;         // the bf16 shadow of p; null = none
+    const float* g;
+    float *m, *v;        // AdamW only
+    OptimHp hp;
+    const ClipRec* rec;  // null = unclipped
+    EmaArg ema;          // e null = no EMA
+    GroupTab gt;
+    int tile_begin, ntiles;
+    long long n;
+};
+
+// the workgroups of a tiled launch over ntiles tiles (8 per CU, the rest grid-strided)
+int group_grid(int ntiles);
+// Launches the instantiation for (kind, tiled, a.rec, a.pbf, a.ema.e) on st; an empty range launches
+// nothing.  SGD without a shadow has no EMA instantiation (fp32 mode runs ema_update behind the step):
+// that combination is an error, as is a flat range that is not whole aligned float4s.
+void optimizer_launch(OptKind kind, const OptimArgs& a, bool tiled, hipStream_t st);
+}  // namespace vit

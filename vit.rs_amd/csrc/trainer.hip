@@ -20,6 +20,7 @@
 
 #include "augment.h"
 #include "ops_internal.h"
+#include "optimizer.h"
 #include "../../include/vit_trainer.h"
 #include "../../include/vit_checkpoint.h"
 #include "../../include/vit_data.h"
@@ -105,190 +106,6 @@ __global__ void clear_cls_blocks_k(bf16_t* __restrict__ x, int T, long long rows
 __global__ void fill_k(float* p, float v, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
-}
-// p -= lr*g; pbf = bf16(p)   (optimizer_step, train_vit.rs:737-743, + bf16 shadow)
-// CLIP: g' = c * g (clip_scale: its own rounding) in place of g; the unclipped instantiation is
-// the kernel as it was
-// EMA: also e = ema_blend(e, p') from the value in registers (common.h): one more 16-byte
-// read and write per float4; the EMA = false instantiations are the kernels as they were
-template <bool CLIP, bool EMA>
-__device__ __forceinline__ void sgd_bf16_body(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                                              const float* __restrict__ g, long long n, float lr, float c,
-                                              EmaArg em) {
-    const long long n4 = n / 4;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
-         i += (long long)gridDim.x * blockDim.x) {
-        float4 pv = reinterpret_cast<float4*>(p)[i];
-        float4 gv = reinterpret_cast<const float4*>(g)[i];
-        float4 ev;
-        if (EMA) ev = reinterpret_cast<float4*>(em.e)[i];
-        sgd_update4<CLIP>(pv, gv, lr, c);
-        reinterpret_cast<float4*>(p)[i] = pv;
-        reinterpret_cast<uint2*>(pbf)[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
-        if (EMA) {
-            ema_blend4(ev, pv, em.d, em.omd);
-            reinterpret_cast<float4*>(em.e)[i] = ev;
-        }
-    }
-    for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x) {
-        p[i] = sgd_update(p[i], CLIP ? clip_scale(c, g[i]) : g[i], lr);
-        pbf[i] = f2bf(p[i]);
-        if (EMA) em.e[i] = ema_blend(em.e[i], p[i], em.d, em.omd);
-    }
-}
-constexpr EmaArg NO_EMA{nullptr, 0.f, 0.f};
-__global__ void sgd_bf16_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                           const float* __restrict__ g, long long n, float lr) {
-    sgd_bf16_body<false, false>(p, pbf, g, n, lr, 1.0f, NO_EMA);
-}
-__global__ void sgd_bf16_clip_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                                const float* __restrict__ g, long long n, float lr,
-                                const ClipRec* __restrict__ rec) {
-    sgd_bf16_body<true, false>(p, pbf, g, n, lr, rec->c, NO_EMA);
-}
-// (rec == nullptr in the unclipped instantiation)
-template <bool CLIP>
-__global__ void sgd_bf16_ema_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
-                               long long n, float lr, const ClipRec* __restrict__ rec, EmaArg em) {
-    sgd_bf16_body<CLIP, true>(p, pbf, g, n, lr, CLIP ? rec->c : 1.0f, em);
-}
-// AdamW over the whole arena (oracle ref_adamw_step), + the bf16 shadow.  One
-// pass: reads p, g, m, v and writes p, m, v (+ pbf) = 7 x 4 B (+2 B) per parameter, HBM-bound.
-// CLIP, EMA: as sgd_bf16_body
-template <bool CLIP, bool EMA>
-__device__ __forceinline__ void adamw_body(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                                           const float* __restrict__ g, float* __restrict__ m,
-                                           float* __restrict__ v, long long n, float lr, float b1, float b2,
-                                           float omb1, float omb2, float bc1, float bc2, float eps, float wd,
-                                           float c, EmaArg em) {
-    const long long n4 = n / 4;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
-         i += (long long)gridDim.x * blockDim.x) {
-        float4 pv = reinterpret_cast<float4*>(p)[i];
-        float4 gv = reinterpret_cast<const float4*>(g)[i];
-        float4 mv = reinterpret_cast<float4*>(m)[i];
-        float4 vv = reinterpret_cast<float4*>(v)[i];
-        float4 ev;
-        if (EMA) ev = reinterpret_cast<float4*>(em.e)[i];
-        adamw_update4<CLIP>(pv, gv, mv, vv, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, c);
-        reinterpret_cast<float4*>(p)[i] = pv;
-        reinterpret_cast<float4*>(m)[i] = mv;
-        reinterpret_cast<float4*>(v)[i] = vv;
-        if (pbf)
-            reinterpret_cast<uint2*>(pbf)[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
-        if (EMA) {
-            ema_blend4(ev, pv, em.d, em.omd);
-            reinterpret_cast<float4*>(em.e)[i] = ev;
-        }
-    }
-    for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x) {
-        p[i] = adamw_update(p[i], CLIP ? clip_scale(c, g[i]) : g[i], m[i], v[i], lr, b1, b2, omb1, omb2, bc1,
-                            bc2, eps, wd);
-        if (pbf) pbf[i] = f2bf(p[i]);
-        if (EMA) em.e[i] = ema_blend(em.e[i], p[i], em.d, em.omd);
-    }
-}
-__global__ void adamw_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
-                        float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
-                        float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd) {
-    adamw_body<false, false>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, 1.0f, NO_EMA);
-}
-__global__ void adamw_clip_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
-                             float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
-                             float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd,
-                             const ClipRec* __restrict__ rec) {
-    adamw_body<true, false>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, rec->c, NO_EMA);
-}
-template <bool CLIP>
-__global__ void adamw_ema_k(float* __restrict__ p, bf16_t* __restrict__ pbf, const float* __restrict__ g,
-                            float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
-                            float b2, float omb1, float omb2, float bc1, float bc2, float eps, float wd,
-                            const ClipRec* __restrict__ rec, EmaArg em) {
-    adamw_body<CLIP, true>(p, pbf, g, m, v, n, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd, CLIP ? rec->c : 1.0f, em);
-}
-// ---- parameter groups (common.h GroupTab): the same updates over the tiles
-// [tile_begin, tile_begin + ntiles) of the whole arena, lr_e = lr * lr_mul and wd_e = wd * wd_mul of
-// the tile's segment (uniform per workgroup iteration).  A gradient chunk is a tile sub-range.
-// EM: empty (the kernel as it was, argument list included) or one trailing EmaArg = the EMA instantiation
-__device__ __forceinline__ EmaArg ema_of() { return NO_EMA; }
-__device__ __forceinline__ EmaArg ema_of(EmaArg em) { return em; }
-template <bool CLIP, typename... EM>
-__global__ __launch_bounds__(GROUP_THREADS) void sgd_bf16_groups_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                                                                   const float* __restrict__ g, GroupTab gt,
-                                                                   int tile_begin, int ntiles, float lr,
-                                                                   const ClipRec* __restrict__ rec, EM... ema) {
-    constexpr bool EMA = sizeof...(EM) != 0;
-    const float c = CLIP ? rec->c : 1.0f;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        long long beg;
-        int n4;
-        const int seg = group_tile(gt, tile_begin + t, beg, n4);
-        sgd_group_tile<CLIP, true, EMA>(p, pbf, g, beg, n4, group_hp(lr, gt.lr_mul[seg]), c, ema_of(ema...));
-    }
-}
-template <bool CLIP, typename... EM>
-__global__ __launch_bounds__(GROUP_THREADS) void adamw_groups_k(float* __restrict__ p, bf16_t* __restrict__ pbf,
-                                                                const float* __restrict__ g, float* __restrict__ m,
-                                                                float* __restrict__ v, GroupTab gt, int tile_begin,
-                                                                int ntiles, float lr, float b1, float b2, float omb1,
-                                                                float omb2, float bc1, float bc2, float eps, float wd,
-                                                                const ClipRec* __restrict__ rec, EM... ema) {
-    constexpr bool EMA = sizeof...(EM) != 0;
-    const EmaArg em = ema_of(ema...);
-    const float c = CLIP ? rec->c : 1.0f;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        long long beg;
-        int n4;
-        const int seg = group_tile(gt, tile_begin + t, beg, n4);
-        const float lr_e = group_hp(lr, gt.lr_mul[seg]), wd_e = group_hp(wd, gt.wd_mul[seg]);
-        float4* __restrict__ p4 = reinterpret_cast<float4*>(p + beg);
-        const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + beg);
-        float4* __restrict__ m4 = reinterpret_cast<float4*>(m + beg);
-        float4* __restrict__ v4 = reinterpret_cast<float4*>(v + beg);
-        uint2* __restrict__ s2 = pbf ? reinterpret_cast<uint2*>(pbf + beg) : nullptr;
-        float4* __restrict__ e4 = EMA ? reinterpret_cast<float4*>(em.e + beg) : nullptr;
-        if (n4 == GROUP_TILE4) {  // a full tile: every load issued before the first use
-            float4 pv[GROUP_UNROLL], gv[GROUP_UNROLL], mv[GROUP_UNROLL], vv[GROUP_UNROLL], ev[GROUP_UNROLL];
-#pragma unroll
-            for (int k = 0; k < GROUP_UNROLL; k++) {
-                const int i = threadIdx.x + k * GROUP_THREADS;
-                pv[k] = p4[i];
-                gv[k] = g4[i];
-                mv[k] = m4[i];
-                vv[k] = v4[i];
-                if (EMA) ev[k] = e4[i];
-            }
-#pragma unroll
-            for (int k = 0; k < GROUP_UNROLL; k++) {
-                const int i = threadIdx.x + k * GROUP_THREADS;
-                adamw_update4<CLIP>(pv[k], gv[k], mv[k], vv[k], lr_e, b1, b2, omb1, omb2, bc1, bc2, eps, wd_e, c);
-                p4[i] = pv[k];
-                m4[i] = mv[k];
-                v4[i] = vv[k];
-                if (s2) s2[i] = make_uint2(pack_bf16x2(pv[k].x, pv[k].y), pack_bf16x2(pv[k].z, pv[k].w));
-                if (EMA) {
-                    ema_blend4(ev[k], pv[k], em.d, em.omd);
-                    e4[i] = ev[k];
-                }
-            }
-        } else {
-            for (int i = threadIdx.x; i < n4; i += GROUP_THREADS) {
-                float4 pv = p4[i], mv = m4[i], vv = v4[i];
-                adamw_update4<CLIP>(pv, g4[i], mv, vv, lr_e, b1, b2, omb1, omb2, bc1, bc2, eps, wd_e, c);
-                p4[i] = pv;
-                m4[i] = mv;
-                v4[i] = vv;
-                if (s2) s2[i] = make_uint2(pack_bf16x2(pv.x, pv.y), pack_bf16x2(pv.z, pv.w));
-                if (EMA) {
-                    float4 ev = e4[i];
-                    ema_blend4(ev, pv, em.d, em.omd);
-                    e4[i] = ev;
-                }
-            }
-        }
-    }
 }
 // top-1 of each logits row (first index among equal maxima, as numpy.argmax) and the count of
 // rows whose prediction equals the label (eval path).  One wave per row.
@@ -1937,8 +1754,18 @@ struct Trainer {
     bool early_on = false, early_done = false;
     float early_lr = 0.f;
     void sgd_chunk(int c) {
+        chunk_fan_in(c);
+        // the chunk's flat range, or its tiles of the whole-arena tiled kernel: elementwise, the one pass's bits
+        optimizer_launch(OPT_SGD, optim_args(c, early_lr, false), groups_on, s_comm);
+        if (!ema_fuse(false)) ema_behind(c, s_comm);
+    }
+    // chunk c's gradients are final on s (and, in the bf16 / fp8 backward with concurrency on, on s2 and
+    // ms[1..nmb)): s_comm waits for all of them.  early_on and clip_live each imply two_streams && lowp()
+    // (vit_trainer_train_step, clip_overlap_on), so their chunks always take the side-stream events.
+    void chunk_fan_in(int c) {
         VIT_HIP(hipEventRecord(chunk_ev[c], s));
         VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev[c], 0));
+        if (!(two_streams && lowp())) return;
         VIT_HIP(hipEventRecord(chunk_ev2[c], s2));
         VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev2[c], 0));
         for (int k = 1; k < nmb; k++) {
@@ -1946,30 +1773,6 @@ struct Trainer {
             VIT_HIP(hipEventRecord(e, ms[k]));
             VIT_HIP(hipStreamWaitEvent(s_comm, e, 0));
         }
-        if (groups_on) {  // the whole-arena grouped kernel over the chunk's tiles: the same bits
-            const int t0 = grp_chunk_tile[c], nt = grp_chunk_tile[c + 1] - t0;
-            if (ema_fuse(false)) {
-                sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s_comm>>>(
-                    params, pbf, grads, grp_tab, t0, nt, early_lr, nullptr, ema_arg());
-                ema_launched("sgd_bf16_groups_ema_chunk");
-                return;
-            }
-            sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s_comm>>>(params, pbf, grads, grp_tab, t0, nt,
-                                                                                   early_lr, nullptr);
-            after_launch("sgd_bf16_groups_chunk");
-            ema_behind(c, s_comm);
-            return;
-        }
-        const long long o = chunk_off[c], n = chunk_off[c + 1] - chunk_off[c];
-        if (ema_fuse(false)) {  // the chunk's range of the average with it: elementwise, the whole-arena pass's bits
-            sgd_bf16_ema_k<false><<<grid_for(n / 4, 256), 256, 0, s_comm>>>(params + o, pbf + o, grads + o, n, early_lr,
-                                                                            nullptr, EmaArg{ema + o, ema_d, ema_omd});
-            ema_launched("sgd_bf16_ema_chunk");
-            return;
-        }
-        sgd_bf16_k<<<grid_for(n / 4, 256), 256, 0, s_comm>>>(params + o, pbf + o, grads + o, n, early_lr);
-        after_launch("sgd_bf16_chunk");
-        ema_behind(c, s_comm);
     }
     // Global-norm gradient clipping (option of vit_trainer_set_grad_clip).  The sum of
     // squares of the gradients is taken per gradient chunk (the chunk_off ranges, in every mode, so
@@ -2036,32 +1839,14 @@ struct Trainer {
             sgd_chunk(c);
             return;
         }
-        if (clip_live && !(comm && overlap)) {  // the events of sgd_chunk, then the chunk's partials
-            VIT_HIP(hipEventRecord(chunk_ev[c], s));
-            VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev[c], 0));
-            VIT_HIP(hipEventRecord(chunk_ev2[c], s2));
-            VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev2[c], 0));
-            for (int k = 1; k < nmb; k++) {
-                hipEvent_t e = chunk_evm[(size_t)c * MAXMB + k];
-                VIT_HIP(hipEventRecord(e, ms[k]));
-                VIT_HIP(hipStreamWaitEvent(s_comm, e, 0));
-            }
+        if (clip_live && !(comm && overlap)) {  // the chunk's partials beside the rest of the backward
+            chunk_fan_in(c);
             clip_partials(c, s_comm);
             clip_comm_busy = true;
             return;
         }
         if (!comm || !overlap) return;
-        VIT_HIP(hipEventRecord(chunk_ev[c], s));
-        VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev[c], 0));
-        if (two_streams && lowp()) {  // the chunk's gradients also come from s2 / ms[]
-            VIT_HIP(hipEventRecord(chunk_ev2[c], s2));
-            VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev2[c], 0));
-            for (int k = 1; k < nmb; k++) {
-                hipEvent_t e = chunk_evm[(size_t)c * MAXMB + k];
-                VIT_HIP(hipEventRecord(e, ms[k]));
-                VIT_HIP(hipStreamWaitEvent(s_comm, e, 0));
-            }
-        }
+        chunk_fan_in(c);
         const long long o = chunk_off[c], n = chunk_off[c + 1] - chunk_off[c];
         ncclResult_t r = ncclAllReduce(grads + o, grads + o, (size_t)n, ncclFloat32, ncclSum, comm, s_comm);
         if (r != ncclSuccess) set_error("ncclAllReduce(chunk %d): %s", c, ncclGetErrorString(r));
@@ -2153,7 +1938,7 @@ struct Trainer {
 
     // Exponential moving average of the weights (vit_trainer_set_ema): one fp32 arena in the
     // layout of params, allocated by the first enabling, advanced by every optimizer step while on: inside the
-    // optimizer kernels (bf16 / fp8 mode, AdamW in every mode), or by ema_update behind the fp32 SGD ops.
+    // optimizer kernels (bf16 / fp8 mode, AdamW in every mode), or by ema_update behind the fp32-mode SGD.
     // ema_view (vit_trainer_ema_weights): the two arena pointers are exchanged, so `params` (and with it
     // P(), the shadows' source and get_params) is the average and `ema` the live weights; every call
     // that would train, overwrite or save either is refused until the exchange is undone.
@@ -2161,9 +1946,9 @@ struct Trainer {
     bool ema_on = false, ema_view = false;
     float ema_d = 0.f, ema_omd = 0.f;
     long long ema_updates = 0;
-    // option "ema_fused" (default 1): 0 runs the optimizer kernels as they are without EMA and launches
-    // ema_update behind each on the same stream (12 B per parameter instead of 8; the same bits): the A/B of
-    // tools/bench_ema.py.  fp32-mode SGD goes through the ops of ops.hip and always takes that form.
+    // option "ema_fused" (default 1): 0 launches the optimizer kernels without EMA and ema_update behind
+    // each on the same stream (12 B per parameter instead of 8; the same bits): the A/B of
+    // tools/bench_ema.py.  fp32-mode SGD has no EMA instantiation (optimizer.hip) and always takes that form.
     bool ema_fused = true;
     bool ema_fuse(bool adamw) const { return ema_on && ema_fused && (lowp() || adamw); }
     // the stand-alone update of gradient chunk c (c < 0: the whole arena) behind an un-fused optimizer launch
@@ -2171,11 +1956,6 @@ struct Trainer {
         if (!ema_on) return;
         const long long o = c < 0 ? 0 : chunk_off[c], n = c < 0 ? arena_elems : chunk_off[c + 1] - chunk_off[c];
         ema_update_on(ema + o, params + o, n, ema_d, ema_omd, st);
-    }
-    EmaArg ema_arg() const { return EmaArg{ema, ema_d, ema_omd}; }
-    void ema_launched(const char* what) {
-        after_launch(what);
-        count_hit(VIT_HIT_EMA);
     }
     // s behind the optimizer work of the side streams (early SGD on s_comm, the side pre-work on s2)
     void ema_join() {
@@ -2342,97 +2122,38 @@ struct Trainer {
         const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)adam_t);
         const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)adam_t);
         tbeg(TC_SGD, 0);
-        if (ema_fuse(true)) {
-            adamw_ema(lr, hp, bc1, bc2);
-        } else if (groups_on) {  // one launch over every tile of the arena
-            const int nt = grp_chunk_tile[n_chunks];
-            bf16_t* shadow = lowp() ? pbf : nullptr;
-            if (clip_on()) {
-                clip_norm();
-                adamw_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
-                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, 1.0f - hp.beta1,
-                    1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay, clip_rec);
-                after_launch("adamw_groups_clipped");
-            } else {
-                adamw_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
-                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, 1.0f - hp.beta1,
-                    1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay, nullptr);
-                after_launch("adamw_groups");
-            }
-        } else if (clip_on()) {
-            clip_norm();
-            adamw_clip_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(
-                params, lowp() ? pbf : nullptr, grads, adam_m, adam_v, arena_elems, lr, hp.beta1, hp.beta2,
-                1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay, clip_rec);
-            after_launch("adamw_clipped");
-        } else {
-            adamw_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(
-                params, lowp() ? pbf : nullptr, grads, adam_m, adam_v, arena_elems, lr,
-                hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay);
-            after_launch("adamw");
-        }
+        if (clip_on()) clip_norm();
+        OptimArgs a = optim_args(-1, lr, true);
+        a.m = adam_m;
+        a.v = adam_v;
+        a.hp = OptimHp{lr, hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay};
+        optimizer_launch(OPT_ADAMW, a, groups_on, s);
         if (!ema_fuse(true)) ema_behind(-1, s);
         tend();
         if (lowp()) refresh_transposed();
     }
 
-    // the AdamW launches with the average fused (ema_on): the same grids, the EMA instantiations
-    void adamw_ema(float lr, const vit_adamw_t& hp, float bc1, float bc2) {
-        bf16_t* shadow = lowp() ? pbf : nullptr;
-        const ClipRec* rec = nullptr;
-        if (clip_on()) {
-            clip_norm();
-            rec = clip_rec;
-        }
-        const float omb1 = 1.0f - hp.beta1, omb2 = 1.0f - hp.beta2;
+    // The arguments of the optimizer launch over gradient chunk c (c < 0: the whole arena) from the
+    // trainer's state: the chunk's tiles of the arena with parameter groups on, its flat range otherwise.
+    // rec is the record clip_norm() has written (the caller runs it first); m / v and the AdamW
+    // hyper-parameters are the caller's.
+    OptimArgs optim_args(int c, float lr, bool adamw) const {
+        const long long o = c < 0 || groups_on ? 0 : chunk_off[c];
+        OptimArgs a{};
+        a.p = params + o;
+        a.g = grads + o;
+        if (lowp()) a.pbf = pbf + o;
+        a.hp.lr = lr;
+        if (clip_on()) a.rec = clip_rec;
+        if (ema_fuse(adamw)) a.ema = EmaArg{ema + o, ema_d, ema_omd};
         if (groups_on) {
-            const int nt = grp_chunk_tile[n_chunks];
-            if (rec)
-                adamw_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
-                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, omb1, omb2, bc1, bc2,
-                    hp.eps, hp.weight_decay, rec, ema_arg());
-            else
-                adamw_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(
-                    params, shadow, grads, adam_m, adam_v, grp_tab, 0, nt, lr, hp.beta1, hp.beta2, omb1, omb2, bc1, bc2,
-                    hp.eps, hp.weight_decay, nullptr, ema_arg());
-            ema_launched(rec ? "adamw_groups_ema_clipped" : "adamw_groups_ema");
+            a.gt = grp_tab;
+            a.tile_begin = c < 0 ? 0 : grp_chunk_tile[c];
+            a.ntiles = grp_chunk_tile[c < 0 ? n_chunks : c + 1] - a.tile_begin;
         } else {
-            const int grid = grid_for(arena_elems / 4, 256);
-            if (rec)
-                adamw_ema_k<true><<<grid, 256, 0, s>>>(params, shadow, grads, adam_m, adam_v, arena_elems, lr, hp.beta1,
-                                                       hp.beta2, omb1, omb2, bc1, bc2, hp.eps, hp.weight_decay, rec,
-                                                       ema_arg());
-            else
-                adamw_ema_k<false><<<grid, 256, 0, s>>>(params, shadow, grads, adam_m, adam_v, arena_elems, lr, hp.beta1,
-                                                        hp.beta2, omb1, omb2, bc1, bc2, hp.eps, hp.weight_decay, nullptr,
-                                                        ema_arg());
-            ema_launched(rec ? "adamw_ema_clipped" : "adamw_ema");
+            a.n = c < 0 ? arena_elems : chunk_off[c + 1] - chunk_off[c];
         }
-    }
-    // the bf16 / fp8 SGD launches with the average fused
-    void sgd_ema(float lr) {
-        const ClipRec* rec = nullptr;
-        if (clip_on()) {
-            clip_norm();
-            rec = clip_rec;
-        }
-        if (groups_on) {
-            const int nt = grp_chunk_tile[n_chunks];
-            if (rec)
-                sgd_bf16_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt,
-                                                                                     lr, rec, ema_arg());
-            else
-                sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt,
-                                                                                      lr, nullptr, ema_arg());
-            ema_launched(rec ? "sgd_bf16_groups_ema_clipped" : "sgd_bf16_groups_ema");
-        } else {
-            const int grid = grid_for(arena_elems / 4, 256);
-            if (rec)
-                sgd_bf16_ema_k<true><<<grid, 256, 0, s>>>(params, pbf, grads, arena_elems, lr, rec, ema_arg());
-            else
-                sgd_bf16_ema_k<false><<<grid, 256, 0, s>>>(params, pbf, grads, arena_elems, lr, nullptr, ema_arg());
-            ema_launched(rec ? "sgd_bf16_ema_clipped" : "sgd_bf16_ema");
-        }
+        return a;
     }
 
     void step(float lr) {
@@ -2447,40 +2168,8 @@ struct Trainer {
         }
         finish_allreduce();
         tbeg(TC_SGD, 0);
-        if (ema_fuse(false)) {
-            sgd_ema(lr);
-        } else if (groups_on) {  // one launch over every tile of the arena
-            const int nt = grp_chunk_tile[n_chunks];
-            const ClipRec* rec = nullptr;
-            if (clip_on()) {
-                clip_norm();
-                rec = clip_rec;
-            }
-            if (!lowp()) {
-                sgd_groups(params, grads, grp_tab, 0, nt, lr, rec, s);
-            } else if (rec) {
-                sgd_bf16_groups_k<true><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt, lr, rec);
-                after_launch("sgd_bf16_groups_clipped");
-            } else {
-                sgd_bf16_groups_k<false><<<group_grid(nt), GROUP_THREADS, 0, s>>>(params, pbf, grads, grp_tab, 0, nt, lr,
-                                                                                  nullptr);
-                after_launch("sgd_bf16_groups");
-            }
-        } else if (clip_on()) {
-            clip_norm();
-            if (lowp()) {
-                sgd_bf16_clip_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(params, pbf, grads, arena_elems, lr,
-                                                                                clip_rec);
-                after_launch("sgd_bf16_clipped");
-            } else {
-                sgd_clip(params, grads, arena_elems, lr, clip_rec, s);
-            }
-        } else if (lowp()) {
-            sgd_bf16_k<<<grid_for(arena_elems / 4, 256), 256, 0, s>>>(params, pbf, grads, arena_elems, lr);
-            after_launch("sgd_bf16");
-        } else {
-            sgd(params, grads, arena_elems, lr, s);
-        }
+        if (clip_on()) clip_norm();
+        optimizer_launch(OPT_SGD, optim_args(-1, lr, false), groups_on, s);
         if (!ema_fuse(false)) ema_behind(-1, s);
         tend();
         if (lowp()) refresh_transposed();
