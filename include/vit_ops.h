@@ -150,6 +150,15 @@ void grad_sumsq(double* out, const float* x, long long n);
  * scalar tail for n % 4 (all scalar otherwise).  No reference counterpart: the update the trainer's optimizer
  * kernels fuse for vit_trainer_set_ema, stand-alone; fp32-mode SGD launches it. */
 void ema_update(float* ema, const float* params, long long n, float decay);
+/* One LAMB step (vit_trainer.h vit_trainer_step_lamb) of one tensor as one segment: m, v
+ * advanced as AdamW's step t does, u = mh / (sqrt(vh) + eps) + weight_decay * p, the norms of p and u in double
+ * (fixed order), r = |p| / |u| where the tensor is adapted (weight_decay != 0, or flags & 1 = always adapt) and
+ * both norms are positive, else 1; flags & 2 caps r at 1; p -= (lr * r) * u.  Device pointers, any n >= 1, any
+ * 4-byte alignment; the element functions and the order of the sums per 4096-element tile are the trainer's.
+ * info (device, nullable) receives {|p|, |u|, r}.  t >= 1.  No reference counterpart: the reference trains
+ * with SGD only. */
+void lamb_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+               float eps, float weight_decay, int t, int flags, float* info);
 
 /* ------------------------------------------------------------------ bf16 fast path
  * Build-side extensions with the same conventions; bf16 storage as raw uint16_t, fp32

@@ -97,6 +97,34 @@ int vit_trainer_step(vit_trainer_t* t, float lr); /* waits for the all-reduce, t
  *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g g;  p -= lr (m/(1-b1^t) / (sqrt(v/(1-b2^t)) + eps) + wd p) */
 int vit_trainer_step_adamw(vit_trainer_t* t, float lr, float beta1, float beta2, float eps,
                            float weight_decay);
+/* LAMB (You et al. 2020; timm's Lamb with grad_averaging): AdamW's direction scaled per
+ * tensor and layer (a segment: one entry of vit_layout_query's indexing) by a trust ratio.  With m', v'
+ * advanced and bias-corrected exactly as vit_trainer_step_adamw does (on g' = c * g under clipping) and
+ * lr_e, wd_e the segment's lr and weight decay (parameter groups as for AdamW):
+ *   u = m'/(1-b1^t) / (sqrt(v'/(1-b2^t)) + eps) + wd_e p        per element, every operation rounded to fp32
+ *   wn = (float)sqrt(sum p^2), un = (float)sqrt(sum u^2)        over the segment's own elements, in double,
+ *                                                                fixed order (deterministic, no atomics)
+ *   r = wn / un if the segment is adapted and wn > 0 and un > 0, else 1
+ *   p -= (lr_e * r) u
+ * A segment is adapted if wd_e != 0 (timm: tensors without weight decay keep r = 1), or always under
+ * VIT_LAMB_ALWAYS_ADAPT; VIT_LAMB_TRUST_CLIP caps r at 1 (LAMBC).  Where every r is 1 (weight_decay = 0, no
+ * flags) the step has the bits of vit_trainer_step_adamw in p, m and v.  lr_mul = 0 freezes a segment's
+ * values; its m, v and ratio are still computed.  The state (m, v, t, the stored hyper-parameters) is
+ * AdamW's: the two step kinds may be mixed, both advance t, and a checkpoint saved after LAMB steps is an
+ * AdamW-state file.  The bf16 shadow, the EMA (vit_trainer_set_ema) and the low-precision copies follow
+ * as after an AdamW step; vit_trainer_get_grads still returns the raw gradients.  Waits for the
+ * all-reduce first; data parallelism needs nothing more (identical gradients give identical ratios).
+ * The first call allocates m, v and the per-tile / per-segment buffers (counted in
+ * vit_trainer_device_bytes from then on).  beta1, beta2 outside [0, 1), a negative or non-finite eps or
+ * weight_decay, and unknown flag bits return non-zero + vit_last_error and change nothing; so does a call
+ * while the EMA weights are in use. */
+enum { VIT_LAMB_ALWAYS_ADAPT = 1, VIT_LAMB_TRUST_CLIP = 2 };
+int vit_trainer_step_lamb(vit_trainer_t* t, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int flags);
+/* the last LAMB step's |w|, |u| and trust ratio, each [20 * num_layers] in vit_layout_query's indexing
+ * (unused entries hold 0, 0, 1), and the number of LAMB steps so far.  Any pointer may be NULL.  An error
+ * before the first LAMB step.  Synchronous. */
+int vit_trainer_get_lamb_info(vit_trainer_t* t, float* w_norm, float* u_norm, float* ratio, long long* steps);
 /* ---- global-norm gradient clipping, for vit_trainer_step, vit_trainer_step_adamw
  *      and vit_trainer_train_step.  Before the update the device computes S = sum of g^2 over every
  *      parameter's gradient (every square and sum in double, fixed order: deterministic),

@@ -99,6 +99,7 @@ _SIGS = {
     "sgd_step": (None, [P, P, LL, F]),
     "grad_sumsq": (None, [P, P, LL]),
     "ema_update": (None, [P, P, LL, F]),
+    "lamb_step": (None, [P, P, P, P, LL, F, F, F, F, F, I, I, P]),
     # bf16 extensions
     "matmul_forward_bf16": (None, [P, P, P, P, I, I, I, I]),
     "matmul_backward_bf16": (None, [P, P, P, P, P, P, I, I, I, I]),
@@ -157,6 +158,8 @@ _SIGS = {
                                ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_double), I]),
     "vit_trainer_step_adamw": (I, [P, F, F, F, F, F]),
     "vit_trainer_get_adamw_state": (I, [P, P, P, ctypes.POINTER(I)]),
+    "vit_trainer_step_lamb": (I, [P, F, F, F, F, F, I]),
+    "vit_trainer_get_lamb_info": (I, [P, P, P, P, ctypes.POINTER(LL)]),
     "vit_trainer_set_grad_clip": (I, [P, F]), "vit_trainer_grad_norm": (F, [P]),
     "vit_trainer_set_param_groups": (I, [P, P, P]),
     "vit_trainer_get_param_groups": (I, [P, P, P, ctypes.POINTER(I)]),
@@ -354,6 +357,22 @@ def augment_u8(images, plan, fill=(0, 0, 0)):
     lib().vit_sync()
     check("vit_augment_u8")
     return images
+
+
+LAMB_ALWAYS_ADAPT, LAMB_TRUST_CLIP = 1, 2  # include/vit_trainer.h VIT_LAMB_*
+
+
+def lamb_flags(always_adapt=False, trust_clip=False):
+    return (LAMB_ALWAYS_ADAPT if always_adapt else 0) | (LAMB_TRUST_CLIP if trust_clip else 0)
+
+
+def lamb_step(p, g, m, v, n, lr, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, t=1, always_adapt=False,
+              trust_clip=False, info=None):
+    """One LAMB step of one tensor as one segment (the lamb_step op, include/vit_ops.h): p, g, m, v are
+    DeviceArrays or device addresses of n fp32 elements (any 4-byte alignment), info None or 3 floats on
+    the device that receive |p|, |u| and the trust ratio; synchronous."""
+    call("lamb_step", p, g, m, v, int(n), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+         int(t), lamb_flags(always_adapt, trust_clip), info)
 
 
 # --------------------------------------------------------------------------- checkpoints
@@ -739,6 +758,24 @@ class ViT:
         """AdamW (vit_trainer_step_adamw)."""
         self._ok(lib().vit_trainer_step_adamw(self.h, float(lr), float(beta1), float(beta2),
                                               float(eps), float(weight_decay)), "step_adamw")
+
+    def optimizer_step_lamb(self, lr, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, always_adapt=False,
+                            trust_clip=False):
+        """LAMB: AdamW's direction scaled per tensor and layer by the trust ratio |w| / |u| (DESIGN.md §17;
+        vit_trainer_step_lamb).  Tensors without weight decay keep ratio 1 unless always_adapt; trust_clip
+        caps the ratio at 1.  Shares m, v, t with optimizer_step_adamw."""
+        self._ok(lib().vit_trainer_step_lamb(self.h, float(lr), float(beta1), float(beta2), float(eps),
+                                             float(weight_decay), lamb_flags(always_adapt, trust_clip)), "step_lamb")
+
+    def lamb_info(self):
+        """{"w_norm", "u_norm", "ratio": [20, L] arrays of the last LAMB step (unused entries 0, 0, 1),
+        "steps": LAMB steps so far}; raises before the first (vit_trainer_get_lamb_info; synchronous)."""
+        shape = (len(data.PARAM_NAMES), self.cfg.num_layers)
+        w, u, r = (np.empty(shape, np.float32) for _ in range(3))
+        n = LL()
+        self._ok(lib().vit_trainer_get_lamb_info(self.h, w.ctypes.data_as(P), u.ctypes.data_as(P),
+                                                 r.ctypes.data_as(P), ctypes.byref(n)), "get_lamb_info")
+        return {"w_norm": w, "u_norm": u, "ratio": r, "steps": int(n.value)}
 
     def set_grad_clip(self, max_norm):
         """Global-norm gradient clipping for every later optimizer step: max_norm > 0 (inf: compute

@@ -195,19 +195,33 @@ __device__ __forceinline__ void ema_blend4(float4& ev, const float4& pv, float d
 // AdamW (oracle ref_adamw_step): one element, every operation rounded like the
 // oracle's line-by-line C (no contraction, correctly rounded sqrt / divide).  omb1 = 1-beta1, omb2 = 1-beta2,
 // bc1/bc2 = the bias corrections 1 - beta^t, computed on the host exactly as the oracle does.
-__device__ __forceinline__ float adamw_update(float p, float g, float& m, float& v, float lr,
-                                              float b1, float b2, float omb1, float omb2,
-                                              float bc1, float bc2, float eps, float wd) {
+// In two halves, which LAMB shares: the direction u = mh / (sqrt(vh) + eps) + wd * p from the
+// moments as stored (adamw_direction; LAMB's second pass calls it again on the stored m', v' and gets the
+// same bits), the moments' advance in front of it (adamw_moments), and the subtraction p - lr * u.
+__device__ __forceinline__ float adamw_direction(float p, float mi, float vi, float bc1, float bc2, float eps,
+                                                 float wd) {
+#pragma clang fp contract(off)
+    // '/' and __builtin_sqrtf are IEEE-rounded under hipcc's default
+    // -fhip-fp32-correctly-rounded-divide-sqrt; __fsqrt_rn is NOT (it maps to the native,
+    // approximate v_sqrt unless OCML_BASIC_ROUNDED_OPERATIONS is defined)
+    const float mh = mi / bc1, vh = vi / bc2;
+    return mh / (__builtin_sqrtf(vh) + eps) + wd * p;
+}
+__device__ __forceinline__ float adamw_moments(float p, float g, float& m, float& v, float b1, float b2,
+                                               float omb1, float omb2, float bc1, float bc2, float eps,
+                                               float wd) {
 #pragma clang fp contract(off)
     const float mi = b1 * m + omb1 * g;
     const float vi = b2 * v + omb2 * g * g;
     m = mi;
     v = vi;
-    // '/' and __builtin_sqrtf are IEEE-rounded under hipcc's default
-    // -fhip-fp32-correctly-rounded-divide-sqrt; __fsqrt_rn is NOT (it maps to the native,
-    // approximate v_sqrt unless OCML_BASIC_ROUNDED_OPERATIONS is defined)
-    const float mh = mi / bc1, vh = vi / bc2;
-    return p - lr * (mh / (__builtin_sqrtf(vh) + eps) + wd * p);
+    return adamw_direction(p, mi, vi, bc1, bc2, eps, wd);
+}
+__device__ __forceinline__ float adamw_update(float p, float g, float& m, float& v, float lr,
+                                              float b1, float b2, float omb1, float omb2,
+                                              float bc1, float bc2, float eps, float wd) {
+#pragma clang fp contract(off)
+    return p - lr * adamw_moments(p, g, m, v, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
 }
 
 // Parameter groups: per-(tensor, layer) multipliers of lr and weight decay inside

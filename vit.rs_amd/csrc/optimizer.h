@@ -32,4 +32,22 @@ int group_grid(int ntiles);
 // nothing.  SGD without a shadow has no EMA instantiation (fp32 mode runs ema_update behind the step):
 // that combination is an error, as is a flat range that is not whole aligned float4s.
 void optimizer_launch(OptKind kind, const OptimArgs& a, bool tiled, hipStream_t st);
+
+// LAMB: AdamW's direction u scaled per segment by the trust ratio |w| / |u|, in three
+// launches: the moments and the per-tile sums of p^2 and u^2, the ratio per segment, the update.
+// Tiled: o is an AdamW tiled range over ALL tiles of o.gt (a ratio needs its whole segment), seg_len[s] the
+// segment's own elements (the sums and the update stop there: the padding behind is not touched).
+// Flat (the lamb_step op): one segment of o.n elements from o.p / o.g / o.m / o.v, any alignment.
+constexpr int LAMB_REC = 3;  // floats per segment record: |w|, |u|, ratio
+struct LambArgs {
+    OptimArgs o;
+    const long long* seg_len;  // [nseg], tiled only
+    double2* slots;            // [tiles] {sum p^2, sum u^2} of each tile, by global tile number
+    float* rec;                // [nseg * LAMB_REC] (flat: one record)
+    int flags;                 // VIT_LAMB_*
+};
+__host__ __device__ inline int lamb_tiles(long long n) {  // tiles of a flat range
+    return (int)((n + GROUP_TILE - 1) / GROUP_TILE);
+}
+void optimizer_launch(const LambArgs& a, bool tiled, hipStream_t st);
 }  // namespace vit

@@ -2106,6 +2106,7 @@ struct Trainer {
         if (has_error()) return false;
         grp_lr.swap(nl);
         grp_wd.swap(nw);
+        grp_dev_ones = false;
         groups_on = true;
         return true;
     }
@@ -2128,6 +2129,75 @@ struct Trainer {
         a.v = adam_v;
         a.hp = OptimHp{lr, hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay};
         optimizer_launch(OPT_ADAMW, a, groups_on, s);
+        if (!ema_fuse(true)) ema_behind(-1, s);
+        tend();
+        if (lowp()) refresh_transposed();
+    }
+    // LAMB (vit_trainer_step_lamb): AdamW's state and direction, the step of every segment
+    // scaled by its trust ratio.  Always the tiled range of the parameter-group tables (a ratio is per
+    // segment), with all-ones multipliers while groups are off.  On the first step: the tables, the
+    // segments' own lengths, a {sum p^2, sum u^2} slot per tile and a {|w|, |u|, r} record per segment.
+    long long* lamb_len = nullptr;
+    double2* lamb_slots = nullptr;
+    float* lamb_rec = nullptr;
+    long long lamb_steps = 0;
+    bool grp_dev_ones = false;  // the device multiplier tables hold all ones (filled here, not by set_groups)
+    bool lamb_enable() {
+        if (lamb_rec) return true;
+        if (!groups_enable()) return false;
+        const int nseg = grp_tab.nseg;
+        std::vector<long long> len(nseg);
+        for (int sgi = 0; sgi < nseg; sgi++) {
+            const int ti = grp_seg_entry[sgi] / L;
+            len[sgi] = layered(ti) ? canon_size[ti] / L : canon_size[ti];
+        }
+        long long* d_len = alloc<long long>(nseg);
+        if (!d_len) return false;
+        VIT_HIP(hipMemcpyAsync(d_len, len.data(), (size_t)nseg * sizeof(long long), hipMemcpyHostToDevice, s));
+        VIT_HIP(hipStreamSynchronize(s));
+        if (has_error()) return false;
+        double2* slots = alloc<double2>(grp_chunk_tile[n_chunks]);  // (every tile of the arena)
+        float* rec = alloc<float>((long long)nseg * LAMB_REC);
+        if (!slots || !rec) return false;
+        lamb_len = d_len;
+        lamb_slots = slots;
+        lamb_rec = rec;
+        return true;
+    }
+    void step_lamb(float lr, const vit_adamw_t& hp, int flags) {
+        pre_side_wait();
+        finish_allreduce();
+        if (!ensure_adam() || !lamb_enable()) return;
+        if (!groups_on && !grp_dev_ones) {  // the bits of 1.0f into both tables, on the device
+            VIT_HIP(hipMemsetD32Async((hipDeviceptr_t)grp_dev_lr, 0x3f800000, grp_tab.nseg, s));
+            VIT_HIP(hipMemsetD32Async((hipDeviceptr_t)grp_dev_wd, 0x3f800000, grp_tab.nseg, s));
+            grp_dev_ones = true;
+        }
+        adam_t += 1;
+        adam_hp = hp;
+        lamb_steps += 1;
+        if (ema_on) ema_updates++;
+        const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)adam_t);
+        const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)adam_t);
+        tbeg(TC_SGD, 0);
+        if (clip_on()) clip_norm();
+        LambArgs a{};
+        a.o.p = params;
+        a.o.g = grads;
+        if (lowp()) a.o.pbf = pbf;
+        a.o.m = adam_m;
+        a.o.v = adam_v;
+        a.o.hp = OptimHp{lr, hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay};
+        if (clip_on()) a.o.rec = clip_rec;
+        if (ema_fuse(true)) a.o.ema = EmaArg{ema, ema_d, ema_omd};
+        a.o.gt = grp_tab;
+        a.o.tile_begin = 0;
+        a.o.ntiles = grp_chunk_tile[n_chunks];
+        a.seg_len = lamb_len;
+        a.slots = lamb_slots;
+        a.rec = lamb_rec;
+        a.flags = flags;
+        optimizer_launch(a, true, s);
         if (!ema_fuse(true)) ema_behind(-1, s);
         tend();
         if (lowp()) refresh_transposed();
@@ -2496,6 +2566,53 @@ int vit_trainer_step_adamw(vit_trainer_t* h, float lr, float beta1, float beta2,
     if (!h->t.ema_unlocked("vit_trainer_step_adamw")) return 1;
     h->t.step_adamw(lr, vit_adamw_t{beta1, beta2, eps, weight_decay});
     return vit::has_error();
+}
+int vit_trainer_step_lamb(vit_trainer_t* h, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          int flags) {
+    if (!h) {
+        set_error("vit_trainer_step_lamb: null trainer");
+        return 1;
+    }
+    if (!h->t.ema_unlocked("vit_trainer_step_lamb")) return 1;
+    if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f)) {
+        set_error("vit_trainer_step_lamb: beta1 %g / beta2 %g outside [0, 1)", (double)beta1, (double)beta2);
+        return 1;
+    }
+    if (!(std::isfinite(eps) && eps >= 0.f && std::isfinite(weight_decay) && weight_decay >= 0.f)) {
+        set_error("vit_trainer_step_lamb: eps %g / weight_decay %g is not finite and >= 0", (double)eps,
+                  (double)weight_decay);
+        return 1;
+    }
+    if (flags & ~(VIT_LAMB_ALWAYS_ADAPT | VIT_LAMB_TRUST_CLIP)) {
+        set_error("vit_trainer_step_lamb: unknown flag bits 0x%x", flags);
+        return 1;
+    }
+    h->t.step_lamb(lr, vit_adamw_t{beta1, beta2, eps, weight_decay}, flags);
+    return vit::has_error();
+}
+int vit_trainer_get_lamb_info(vit_trainer_t* h, float* w_norm, float* u_norm, float* ratio, long long* steps) {
+    if (!h) {
+        set_error("vit_trainer_get_lamb_info: null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    if (steps) *steps = t.lamb_steps;
+    if (!t.lamb_steps) {
+        set_error("vit_trainer_get_lamb_info: no LAMB step has run");
+        return 1;
+    }
+    const int nseg = t.grp_tab.nseg;
+    std::vector<float> rec((size_t)nseg * vit::LAMB_REC);
+    VIT_HIP(hipMemcpyAsync(rec.data(), t.lamb_rec, rec.size() * 4, hipMemcpyDeviceToHost, t.s));
+    VIT_HIP(hipStreamSynchronize(t.s));
+    if (vit::has_error()) return 1;
+    float* out[vit::LAMB_REC] = {w_norm, u_norm, ratio};
+    for (int k = 0; k < vit::LAMB_REC; k++) {
+        if (!out[k]) continue;
+        for (int e = 0; e < 20 * t.L; e++) out[k][e] = k == 2 ? 1.0f : 0.0f;
+        for (int sgi = 0; sgi < nseg; sgi++) out[k][t.grp_seg_entry[sgi]] = rec[(size_t)sgi * vit::LAMB_REC + k];
+    }
+    return 0;
 }
 int vit_trainer_set_grad_clip(vit_trainer_t* h, float max_norm) {
     if (!h || !(max_norm >= 0.f)) {
