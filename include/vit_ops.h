@@ -68,7 +68,10 @@ enum {
                                         2 out-of-place apply (sharpness, affine), 3 copy back */
     VIT_HIT_EMA = 95,                /* a launch that advances an EMA of the weights: an optimizer kernel's EMA
                                         instantiation (vit_trainer_set_ema) or ema_update */
-    VIT_HIT_COUNT = 96
+    VIT_HIT_ERASE = 96,              /* random erasing on the fp32 batch (vit_random_erase_f32, vit_trainer_erase_batch):
+                                        one launch per call that has a non-empty box.  A family of its own: the mix
+                                        kernels of vit_trainer_mix_batch are in no family */
+    VIT_HIT_COUNT = 97
 };
 int vit_kernel_hits(long long* out, int n); /* copies min(n, VIT_HIT_COUNT); returns VIT_HIT_COUNT */
 void vit_kernel_hits_reset(void);
@@ -335,6 +338,33 @@ void gemm_bf16_set_debug(int flags);
  * 2 end of wave 0, 3 hardware id = XCC_ID << 32 | HW_ID, 4 + w end of wave w, 12 first K-step's
  * operands landed); NULL turns it off */
 void gemm_bf16_set_trace(unsigned long long* trace);
+/* ------------------------------------------------------------------ random erasing
+ * timm's RandomErasing on a normalised fp32 batch: dev_pixels [batch][3][img][img] (device, any 4-byte
+ * alignment), in place, on stream (a hipStream_t; NULL = the context stream).  host_boxes
+ * [batch][max_count][4] = x0, y0, x1, y1 per box, the box being [x0, x1) x [y0, y1) of all three channel
+ * planes; a box with x0 == x1 or y0 == y1 is empty.  Pixels outside every box keep their bits.  Inside:
+ *   VIT_ERASE_CONST  +0.0f;
+ *   VIT_ERASE_PIXEL  z(p) at the absolute position p = (c * img + y) * img + x of the image, so overlapping
+ *                    boxes agree and a pixel's value does not depend on the box that covers it;
+ *   VIT_ERASE_RAND   one colour per box and channel: z(3 * img * img + 3 * k + c) for box k (where boxes
+ *                    overlap, the colour of the box with the largest k, as erasing them in order gives).
+ * Every covered pixel is written once, by the last box that covers it.
+ * z(p) of image b: sn = seed ^ splitmix64(0x65726e6f697365 (ASCII "ernoise"), host_keys[b]) (the counter-form
+ * splitmix64 of vit_drop_path_draw), w = the word of the stream sn at position p, and in double
+ *   u1 = ((w >> 40) + 1) * 2^-24                 in (0, 1]
+ *   u2 = ((w >> 16) & 0xFFFFFF) * 2^-24          in [0, 1)
+ *   z  = (float)( sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2) )
+ * Box-Muller with every operation one rounded double operation and one rounding to fp32 (no FMA can form),
+ * so the result depends on (seed, key, p) alone: not on the batch, the slot or the box.
+ * The host validates everything before any GPU work: a box not 0 <= x0 <= x1 <= img, 0 <= y0 <= y1 <= img,
+ * max_count outside 1..4, an unknown mode, host_keys == NULL in a noise mode (CONST may pass NULL), img
+ * outside 1..8192 or more than 65535 boxes return non-zero with vit_last_error and leave the batch
+ * untouched.  The non-empty boxes go to the device as one small asynchronous copy and one launch covers
+ * them all; a call without a non-empty box launches nothing.  Returns once the host arrays have been
+ * read. */
+enum { VIT_ERASE_CONST = 0, VIT_ERASE_RAND = 1, VIT_ERASE_PIXEL = 2 };
+int vit_random_erase_f32(float* dev_pixels, int batch, int img, const int* host_boxes, int max_count, int mode,
+                         unsigned long long seed, const long long* host_keys, void* stream);
 void convert_f32_to_bf16(uint16_t* out, const float* inp, long long n);
 void convert_bf16_to_f32(float* out, const uint16_t* inp, long long n);
 

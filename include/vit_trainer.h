@@ -189,6 +189,21 @@ int vit_trainer_set_drop_path(vit_trainer_t* t, const float* host_scales);
 /* the table the last training forward used into out ([num_layers][2][batch], nullable); *used (nullable)
  * = 0 if that forward ran without one (out is then left as it is) */
 int vit_trainer_get_drop_path(vit_trainer_t* t, float* out, int* used);
+/* ---- random erasing (timm's RandomErasing, DeiT: prob 0.25, pixel mode, one box): erase the
+ *      current device batch in place on the trainer's stream with vit_random_erase_f32 (vit_ops.h: the boxes
+ *      [batch][max_count][4], the modes VIT_ERASE_CONST / _RAND / _PIXEL, the normal z(p), the errors).  Call
+ *      after any vit_trainer_set_batch* variant (it is ordered behind the u8 and JPEG paths' normalise) and
+ *      before vit_trainer_mix_batch: erase first, then mix, timm's order without the prefetcher.  Works with
+ *      or without labels and in every precision mode; touches only the pixels.  Non-zero + vit_last_error,
+ *      the batch left as it was, on a bad argument, after vit_trainer_mix_batch of the same batch ("the batch
+ *      is already mixed") and on a second erase of the same batch ("already erased"); every set_batch*
+ *      resets both states.  Returns once the host arrays have been read (no wait for the stream).  The
+ *      device list buffer is allocated by the first call that has a box and counted in
+ *      vit_trainer_device_bytes.  Nothing is written to checkpoints; a trainer that never calls it issues the
+ *      launches it always did.  The caller chooses the keys: epoch * N + record where it knows the record,
+ *      (step * world + rank) * batch + i otherwise, so that ranks draw different boxes. ---- */
+int vit_trainer_erase_batch(vit_trainer_t* t, const int* host_boxes, int max_count, int mode,
+                            unsigned long long seed, const long long* host_keys);
 /* host-only draw of such a table (no GPU call), out [num_layers][2][batch]:
  *   p_l = linear ? (float)((double)rate * l / (num_layers - 1)) : rate   (rate for num_layers == 1; timm's
  *         linspace(0, rate, depth));
@@ -200,6 +215,27 @@ int vit_trainer_get_drop_path(vit_trainer_t* t, float* out, int* used);
  * [0, 1) (or a bad size): non-zero + vit_last_error. */
 int vit_drop_path_draw(unsigned long long seed, long long key, int num_layers, int batch, float rate,
                        int linear, float* out);
+/* host-only draw of one square image's erase boxes (no GPU call): timm's RandomErasing._erase on the
+ * project's generator.  boxes [max_count][4] = x0, y0, x1, y1 (boxes past *count and failed boxes are
+ * 0, 0, 0, 0), *count = the number of boxes drawn (0: the image is not erased).
+ *   w_k = word k of the splitmix64 counter stream of s = seed ^ splitmix64(0x6572617365, key) (ASCII
+ *         "erase"); every uniform is u = (w >> 11) * 2^-53 in double;
+ *   w_0: the image is erased iff u < prob;
+ *   w_1: count = min_count + floor(u * (max_count - min_count + 1)) (consumed even when the two are equal);
+ *   box k, attempt a of 10: u0 .. u3 from the words 2 + (k * 10 + a) * 4 + {0, 1, 2, 3}:
+ *     target = (min_area + u0 * (max_area - min_area)) * (img * img) / count
+ *     aspect = exp(log(min_aspect) + u1 * (log(max_aspect) - log(min_aspect)))
+ *     h = (int)rint(sqrt(target * aspect)), w = (int)rint(sqrt(target / aspect))   (ties to even)
+ *     if w < img and h < img: top = floor(u2 * (img - h + 1)), left = floor(u3 * (img - w + 1)), the box is
+ *     [left, left + w) x [top, top + h) and the attempts end; after ten failures the box is empty
+ *   (all in double, evaluated left to right as written, with the C library's exp / log / sqrt).
+ * Word positions are fixed and the draw is stateless: the boxes depend on (seed, key) and the arguments
+ * only.  timm's defaults: min_area 0.02, max_area 1/3, min_aspect 0.3, max_aspect 1/0.3, counts 1, 1.
+ * prob outside [0, 1], areas not 0 < min <= max <= 1, aspects not 0 < min <= max, counts not
+ * 1 <= min <= max <= 4, img < 1: non-zero + vit_last_error, the outputs untouched. */
+int vit_random_erase_draw(unsigned long long seed, long long key, int img, double prob, double min_area,
+                          double max_area, double min_aspect, double max_aspect, int min_count, int max_count,
+                          int* boxes, int* count);
 /* ---- exponential moving average of the weights (timm's ModelEmaV2): one more fp32 arena e,
  *      advanced by every optimizer step while on.  With d the decay and omd = (float)(1.0 - (double)d), taken
  *      once on the host, for every element

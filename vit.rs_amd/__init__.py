@@ -26,9 +26,11 @@ from . import groups  # noqa: E402  (parameter-group tables: no_decay, layer_dec
 from . import augment  # noqa: E402  (RandAugment: the policy draw and its numpy statement)
 from . import droppath  # noqa: E402  (stochastic depth: the per-step table draw)
 from . import ema  # noqa: E402  (EMA of the weights: the warm-up schedule and the numpy statement)
+from . import erase  # noqa: E402  (random erasing: the box draw and the numpy statement)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
+ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2  # include/vit_ops.h VIT_ERASE_*
 _lib = None
 
 
@@ -72,6 +74,7 @@ _VOID = [("vit_clear_error", []), ("vit_set_stream", [ctypes.c_void_p]),
 
 # name -> (restype, argtypes)
 P, I, LL, F, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t
+D = ctypes.c_double
 _SIGS = {
     "vit_init": (I, [I]), "vit_get_stream": (P, []), "vit_sync": (I, []),
     "vit_last_error": (I, [ctypes.POINTER(ctypes.c_char_p)]),
@@ -171,6 +174,9 @@ _SIGS = {
     "vit_trainer_set_drop_path": (I, [P, P]),
     "vit_trainer_get_drop_path": (I, [P, P, ctypes.POINTER(I)]),
     "vit_drop_path_draw": (I, [ctypes.c_ulonglong, LL, I, I, F, I, P]),
+    "vit_random_erase_draw": (I, [ctypes.c_ulonglong, LL, I, D, D, D, D, D, I, I, P, ctypes.POINTER(I)]),
+    "vit_random_erase_f32": (I, [P, I, I, P, I, I, ctypes.c_ulonglong, P, P]),
+    "vit_trainer_erase_batch": (I, [P, P, I, I, ctypes.c_ulonglong, P]),
     # checkpoints (include/vit_checkpoint.h; host-only)
     "vit_config_num_params": (LL, [ctypes.POINTER(VitConfigC)]),
     "vit_checkpoint_read_info": (I, [ctypes.c_char_p, P]),
@@ -241,6 +247,7 @@ HIT_LN_MX = 89
 HIT_LNB_MX = 90
 HIT_AUGMENT = 91  # + 0 statistics / LUT, 1 in-place apply, 2 out-of-place apply, 3 copy back
 HIT_EMA = 95  # a launch that advances an EMA of the weights (fused optimizer kernel or ema_update)
+HIT_ERASE = 96  # random erasing: one launch per call that has a non-empty box
 
 
 def kernel_hits():
@@ -357,6 +364,36 @@ def augment_u8(images, plan, fill=(0, 0, 0)):
     lib().vit_sync()
     check("vit_augment_u8")
     return images
+
+
+def _erase_args(boxes, batch, mode, keys):
+    """(boxes int32 [batch, max_count, 4], max_count, keys int64 [batch] or None) for the erase calls; shapes
+    only: the library validates the values."""
+    bx = np.ascontiguousarray(boxes, dtype=np.int32)
+    assert bx.ndim == 3 and bx.shape[0] == batch and bx.shape[2] == 4, bx.shape
+    ks = None
+    if keys is not None:
+        ks = np.ascontiguousarray(keys, dtype=np.int64)
+        assert ks.shape == (batch,), ks.shape
+    return bx, int(bx.shape[1]), ks
+
+
+def random_erase(pixels, boxes, mode=ERASE_PIXEL, seed=0, keys=None):
+    """Erase the boxes [batch, max_count, 4] = x0, y0, x1, y1 of a DeviceArray float32 [batch, 3, img, img] in
+    place on the context stream (vit_random_erase_f32): ERASE_CONST zeros, ERASE_RAND one normal colour per
+    box and channel, ERASE_PIXEL per-pixel normals of the streams of `seed` and keys [batch] (see
+    erase.reference_apply); synchronous."""
+    assert pixels.dtype == np.float32 and len(pixels.shape) == 4 and pixels.shape[1] == 3
+    assert pixels.shape[2] == pixels.shape[3]
+    bx, max_count, ks = _erase_args(boxes, pixels.shape[0], mode, keys)
+    if lib().vit_random_erase_f32(pixels.ptr, pixels.shape[0], pixels.shape[2], bx.ctypes.data_as(P), max_count,
+                                  int(mode), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)),
+                                  ks.ctypes.data_as(P) if ks is not None else None, None):
+        check("vit_random_erase_f32")
+        raise VitError("vit_random_erase_f32 failed")
+    lib().vit_sync()
+    check("vit_random_erase_f32")
+    return pixels
 
 
 LAMB_ALWAYS_ADAPT, LAMB_TRUST_CLIP = 1, 2  # include/vit_trainer.h VIT_LAMB_*
@@ -727,6 +764,16 @@ class ViT:
         MIX_MIXUP with lam, or MIX_CUTMIX with box = (x0, y0, x1, y1); e.g. *Mixer.draw(img)."""
         x0, y0, x1, y1 = (int(c) for c in box) if box is not None else (0, 0, 0, 0)
         self._ok(lib().vit_trainer_mix_batch(self.h, int(mode), float(lam), x0, y0, x1, y1), "mix_batch")
+
+    def erase_batch(self, boxes, mode=ERASE_PIXEL, seed=0, keys=None):
+        """Random erasing of the current device batch in place (vit_trainer_erase_batch): boxes
+        [B, max_count, 4] = x0, y0, x1, y1, mode ERASE_CONST / ERASE_RAND / ERASE_PIXEL, the noise streams of
+        `seed` and keys [B] (None only for ERASE_CONST).  After set_batch*, before mix_batch, once per batch;
+        see erase.Eraser."""
+        bx, max_count, ks = _erase_args(boxes, self.B, mode, keys)
+        self._ok(lib().vit_trainer_erase_batch(self.h, bx.ctypes.data_as(P), max_count, int(mode),
+                                               ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)),
+                                               ks.ctypes.data_as(P) if ks is not None else None), "erase_batch")
 
     def pixels(self):
         """The current device batch [B, 3, img, img] fp32, mixed or not (synchronous)."""

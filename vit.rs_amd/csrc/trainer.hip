@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "augment.h"
+#include "erase.h"
 #include "ops_internal.h"
 #include "optimizer.h"
 #include "../../include/vit_trainer.h"
@@ -257,6 +258,11 @@ struct Trainer {
     bool mixed = false;
     float mix_lam = 1.f;
     int* labels_b = nullptr;
+    // random erasing of the current batch (erase.hip; reset with `mixed`): the device list of
+    // boxes is allocated by the first erase that has one, the pinned staging by erase::enqueue
+    bool erased = false;
+    void* erase_list = nullptr;
+    erase::Stage erase_stage;
     bool two_labels() const { return mixed && mix_lam != 1.0f; }
     bool soft_targets() const { return smooth_eps > 0.f || two_labels(); }
     int* preds = nullptr;     // eval: [B] top-1 + one counter
@@ -914,6 +920,7 @@ struct Trainer {
             if (dp_stage[k]) (void)hipHostFree(dp_stage[k]);
             if (dp_staged[k]) (void)hipEventDestroy(dp_staged[k]);
         }
+        erase_stage.release();
         for (auto& a : allocs) (void)hipFree(a.p);
         for (auto e : chunk_ev) (void)hipEventDestroy(e);
         for (auto e : chunk_ev2) (void)hipEventDestroy(e);
@@ -1912,6 +1919,7 @@ struct Trainer {
         VIT_HIP(hipStreamWaitEvent(s, u8_copied[k], 0));
         has_targets = lab != nullptr;
         mixed = false;
+        erased = false;
         const long long n = (long long)B * HW;
         normalize_u8_k<<<cdiv(n, 256), 256, 0, s>>>(pixels, labels, u8_stage[k], lab ? lab_stage[k] : nullptr,
                                                      B, HW, mean[0], mean[1], mean[2], sd[0], sd[1], sd[2]);
@@ -2361,6 +2369,7 @@ int vit_trainer_set_batch(vit_trainer_t* h, const float* px, const int* lab) {
     VIT_HIP(hipMemcpyAsync(t.pixels, px, (size_t)t.B * 3 * t.cfg.img * t.cfg.img * 4, hipMemcpyHostToDevice, t.s));
     t.has_targets = lab != nullptr;
     t.mixed = false;
+    t.erased = false;
     if (lab) VIT_HIP(hipMemcpyAsync(t.labels, lab, (size_t)t.B * 4, hipMemcpyHostToDevice, t.s));
     VIT_HIP(hipStreamSynchronize(t.s));
     return vit::has_error();
@@ -2370,6 +2379,7 @@ int vit_trainer_set_batch_device(vit_trainer_t* h, const float* px, const int* l
     VIT_HIP(hipMemcpyAsync(t.pixels, px, (size_t)t.B * 3 * t.cfg.img * t.cfg.img * 4, hipMemcpyDeviceToDevice, t.s));
     t.has_targets = lab != nullptr;
     t.mixed = false;
+    t.erased = false;
     if (lab) VIT_HIP(hipMemcpyAsync(t.labels, lab, (size_t)t.B * 4, hipMemcpyDeviceToDevice, t.s));
     return vit::has_error();
 }
@@ -2424,6 +2434,32 @@ int vit_trainer_mix_batch(vit_trainer_t* h, int mode, float lam, int x0, int y0,
     if (vit::has_error()) return 1;
     t.mixed = true;
     t.mix_lam = lam;
+    return 0;
+}
+int vit_trainer_erase_batch(vit_trainer_t* h, const int* host_boxes, int max_count, int mode, unsigned long long seed,
+                            const long long* host_keys) {
+    if (!h) {
+        set_error("vit_trainer_erase_batch: null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    vit::erase::Plan p;
+    if (!vit::erase::prepare(host_boxes, t.B, t.cfg.img, max_count, mode, seed, host_keys, "vit_trainer_erase_batch", p))
+        return 1;
+    if (t.mixed) {
+        set_error("vit_trainer_erase_batch: the batch is already mixed");
+        return 1;
+    }
+    if (t.erased) {
+        set_error("vit_trainer_erase_batch: the batch is already erased");
+        return 1;
+    }
+    if (!p.list.empty() && !t.erase_list) {
+        t.erase_list = t.alloc<char>((long long)vit::erase::list_bytes(t.B));
+        if (!t.erase_list) return 1;
+    }
+    if (!vit::erase::enqueue(p, t.pixels, t.erase_list, t.erase_stage, t.s)) return 1;
+    t.erased = true;
     return 0;
 }
 int vit_trainer_get_pixels(vit_trainer_t* h, float* host) {
