@@ -71,7 +71,9 @@ enum {
     VIT_HIT_ERASE = 96,              /* random erasing on the fp32 batch (vit_random_erase_f32, vit_trainer_erase_batch):
                                         one launch per call that has a non-empty box.  A family of its own: the mix
                                         kernels of vit_trainer_mix_batch are in no family */
-    VIT_HIT_COUNT = 97
+    VIT_HIT_SGDM = 97,               /* momentum SGD: every momentum instantiation of the optimizer kernels
+                                        (vit_trainer_set_sgd) and sgd_momentum_step */
+    VIT_HIT_COUNT = 98
 };
 int vit_kernel_hits(long long* out, int n); /* copies min(n, VIT_HIT_COUNT); returns VIT_HIT_COUNT */
 void vit_kernel_hits_reset(void);
@@ -141,6 +143,18 @@ void patch_embed_backward(float* dpatch_w, float* dpatch_b, float* dcls, float* 
                           int C);
 /* optimizer_step (train_vit.rs:737): params -= lr * grads */
 void sgd_step(float* params, const float* grads, long long n, float lr);
+/* torch.optim.SGD's update with momentum, dampening, Nesterov and coupled weight decay (vit_trainer.h
+ * vit_trainer_set_sgd), per element, every operation rounded to fp32 on its own (no FMA), with
+ * omd = (float)(1.0 - (double)dampening):
+ *     g2 = weight_decay != 0 ? g + weight_decay * p : g
+ *     b' = first ? g2 : momentum * b + omd * g2      (first: buf is seeded with g2's bits, its old values ignored)
+ *     d  = nesterov ? g2 + momentum * b' : b'
+ *     p' = p - lr * d
+ * Device pointers, any n >= 0, any 4-byte alignment: the scalar form of the element function the trainer's
+ * momentum kernels run.  Every value must be finite, momentum and weight_decay >= 0, and nesterov needs
+ * momentum > 0 and dampening == 0 (torch's rule).  No reference counterpart: the reference's SGD is sgd_step. */
+void sgd_momentum_step(float* p, const float* g, float* buf, long long n, float lr, float momentum, float dampening,
+                       float weight_decay, int nesterov, int first);
 /* out[0] = sum_i x[i]^2: every square and every sum in double; device pointers; any n >= 0
  * (n == 0 gives 0).  No reference counterpart: the reduction behind the trainer's global-norm
  * gradient clipping (vit_trainer_set_grad_clip), which runs this kernel body per gradient chunk.

@@ -151,7 +151,8 @@ float vit_trainer_grad_norm(vit_trainer_t* t);
  *      entry e of a parameter's tensor and layer the update runs with lr_e = lr * lr_mul[e] and
  *      wd_e = weight_decay * wd_mul[e], each one fp32 multiply rounded on its own, in place of lr and
  *      weight_decay; under clipping on g' = c * g as before.  1.0f * x == x, so all-ones multipliers
- *      give the bits of the ungrouped step.  SGD has no weight decay and uses lr_mul only.
+ *      give the bits of the ungrouped step.  Plain SGD has no weight decay and uses lr_mul only; momentum SGD
+ *      (vit_trainer_set_sgd) uses both, and its buffer advances for a frozen tensor like AdamW's m and v.
  *      lr_mul == 0 freezes a tensor's values; AdamW's m and v of that tensor still advance (as in a
  *      torch parameter group with lr = 0), and its gradient is still computed.
  *      vit_trainer_grad_norm and the clip factor ignore the groups: the norm is over all raw gradients.
@@ -241,8 +242,8 @@ int vit_random_erase_draw(unsigned long long seed, long long key, int img, doubl
  *      once on the host, for every element
  *          e' = fl32( fl32(d * e) + fl32(omd * p') )
  *      with p' the fp32 master value the step has just written; each product and the sum rounded to fp32 on
- *      its own (no FMA): numpy's fp32 `d * e + omd * p`.  In bf16 / fp8 mode (and for AdamW in every mode) the
- *      update runs inside the optimizer kernels, which hold p' in registers; fp32-mode SGD launches
+ *      its own (no FMA): numpy's fp32 `d * e + omd * p`.  In bf16 / fp8 mode (and for AdamW and momentum SGD in every mode) the
+ *      update runs inside the optimizer kernels, which hold p' in registers; fp32-mode plain SGD launches
  *      ema_update (vit_ops.h) behind its update on the same stream: the same bits.  A trainer that never turns
  *      EMA on issues the launches, allocates the memory and writes the checkpoint bytes it always did.
  *      Data parallelism needs nothing more: every rank holds identical parameters after a step and applies
@@ -264,12 +265,43 @@ int vit_trainer_set_ema_params(vit_trainer_t* t, const float* host);
 /* evaluate with the averaged weights.  on = 1 exchanges the live and the averaged arena (a pointer exchange)
  * and refreshes every derived copy (the bf16 shadow, the transposed copies, the fp8 MX copies): until on = 0,
  * vit_trainer_eval / _forward / _get_logits use the average and vit_trainer_get_params returns it, and
- * vit_trainer_backward, _step, _step_adamw, _train_step, _zero_grad, _set_params, _set_ema, _set_ema_params,
+ * vit_trainer_backward, _step, _step_adamw, _train_step, _zero_grad, _set_params, _set_ema, _set_ema_params, _set_sgd,
  * _load_checkpoint and _save_checkpoint return non-zero ("... EMA weights in use") and change nothing.
  * on = 0 exchanges back and refreshes again: the live fp32 parameters keep their bits and the derived
  * copies, deterministic functions of them, get theirs back.  on = 1 twice, on = 0 while not in use, and
  * on = 1 while EMA is off are errors.  Synchronous; waits for the side streams' work first. */
 int vit_trainer_ema_weights(vit_trainer_t* t, int on);
+/* ---- momentum SGD: torch.optim.SGD's update with momentum, dampening, Nesterov and coupled
+ *      weight decay, as a setting of vit_trainer_step and vit_trainer_train_step (the early per-chunk update
+ *      included), run inside the optimizer kernels.  For one element, with c the clip factor under clipping,
+ *      lr_e = lr * lr_mul and wd_e = weight_decay * wd_mul of the element's parameter group (one fp32 multiply
+ *      each, as for AdamW), mu the momentum and omd = (float)(1.0 - (double)dampening) taken once on the host,
+ *      every operation rounded to fp32 on its own (no FMA):
+ *          g1 = clipping ? c * g : g
+ *          g2 = wd_e != 0 ? g1 + wd_e * p : g1
+ *          b' = first ? g2 : mu * b + omd * g2
+ *          d  = nesterov ? g2 + mu * b' : b'
+ *          p' = p - lr_e * d
+ *      `first` is the first momentum step after the buffer was created or reset (torch's buf = grad.clone(),
+ *      without dampening).  A tensor with lr_mul = 0 keeps its values while its buffer advances.  The EMA reads
+ *      p' and the bf16 shadow gets bf16(p'), as for plain SGD.  The buffer is one more fp32 arena, separate from
+ *      AdamW's m and v: the step kinds may be interleaved and neither touches the other's state;
+ *      vit_trainer_set_params does not touch it.  Under data parallelism every rank must set the same values. ---- */
+/* 0, 0, 0, 0 = plain SGD (the default): the launches, the memory and the checkpoint bytes of a trainer that never
+ * called this.  momentum > 0: the first such step allocates the buffer (arena_elems floats, zeroed, counted in
+ * vit_trainer_device_bytes from then on) and runs with first = 1; every momentum step advances the step count
+ * once (also at lr = 0).  Setting momentum back to 0 keeps the buffer and the count, plain steps do not touch
+ * them, and turning it on again continues from them.  Every value must be finite, momentum >= 0 and
+ * weight_decay >= 0; nesterov needs momentum > 0 and dampening == 0 (torch's rule); weight_decay > 0 needs
+ * momentum > 0 (plain SGD has no decayed form here).  Otherwise, and while the EMA weights are in use:
+ * non-zero + vit_last_error, the previous setting stays.  A hyper-parameter: persists across steps; written to
+ * checkpoints together with the buffer. */
+int vit_trainer_set_sgd(vit_trainer_t* t, float momentum, float dampening, float weight_decay, int nesterov);
+/* the setting in force and the number of momentum steps since the buffer was seeded; any pointer may be NULL */
+int vit_trainer_get_sgd_info(vit_trainer_t* t, float* momentum, float* dampening, float* weight_decay,
+                             int* nesterov, long long* steps);
+/* canonical host copy of the momentum buffer; synchronous; an error before the first momentum step */
+int vit_trainer_get_momentum(vit_trainer_t* t, float* host);
 /* canonical host copies of m, v (either may be NULL) and the step count; synchronous */
 int vit_trainer_get_adamw_state(vit_trainer_t* t, float* m, float* v, int* step);
 /* eval: forward of the current batch, then top-1 per image on the device.

@@ -27,6 +27,7 @@ from . import augment  # noqa: E402  (RandAugment: the policy draw and its numpy
 from . import droppath  # noqa: E402  (stochastic depth: the per-step table draw)
 from . import ema  # noqa: E402  (EMA of the weights: the warm-up schedule and the numpy statement)
 from . import erase  # noqa: E402  (random erasing: the box draw and the numpy statement)
+from . import sgd  # noqa: E402  (momentum SGD: the timm presets and the numpy statement)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
@@ -47,6 +48,11 @@ class VitConfigC(ctypes.Structure):
 class AdamWC(ctypes.Structure):
     _fields_ = [("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
                 ("weight_decay", ctypes.c_float)]
+
+
+class SgdC(ctypes.Structure):
+    _fields_ = [("momentum", ctypes.c_float), ("dampening", ctypes.c_float), ("weight_decay", ctypes.c_float),
+                ("nesterov", ctypes.c_int)]
 
 
 class CheckpointInfoC(ctypes.Structure):
@@ -103,6 +109,7 @@ _SIGS = {
     "grad_sumsq": (None, [P, P, LL]),
     "ema_update": (None, [P, P, LL, F]),
     "lamb_step": (None, [P, P, P, P, LL, F, F, F, F, F, I, I, P]),
+    "sgd_momentum_step": (None, [P, P, P, LL, F, F, F, F, I, I]),
     # bf16 extensions
     "matmul_forward_bf16": (None, [P, P, P, P, I, I, I, I]),
     "matmul_backward_bf16": (None, [P, P, P, P, P, P, I, I, I, I]),
@@ -171,6 +178,10 @@ _SIGS = {
     "vit_trainer_set_ema_params": (I, [P, P]),
     "vit_trainer_get_ema_info": (I, [P, ctypes.POINTER(F), ctypes.POINTER(LL), ctypes.POINTER(I)]),
     "vit_trainer_ema_weights": (I, [P, I]),
+    "vit_trainer_set_sgd": (I, [P, F, F, F, I]),
+    "vit_trainer_get_sgd_info": (I, [P, ctypes.POINTER(F), ctypes.POINTER(F), ctypes.POINTER(F), ctypes.POINTER(I),
+                                     ctypes.POINTER(LL)]),
+    "vit_trainer_get_momentum": (I, [P, P]),
     "vit_trainer_set_drop_path": (I, [P, P]),
     "vit_trainer_get_drop_path": (I, [P, P, ctypes.POINTER(I)]),
     "vit_drop_path_draw": (I, [ctypes.c_ulonglong, LL, I, I, F, I, P]),
@@ -185,6 +196,9 @@ _SIGS = {
     "vit_checkpoint_write_ex": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, P, P, I, P, P, F, LL]),
     "vit_checkpoint_read_ema": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, ctypes.POINTER(F),
                                     ctypes.POINTER(LL), ctypes.POINTER(I)]),
+    "vit_checkpoint_write_sgd": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, P, P, I, P, P, F, LL, P, P, LL]),
+    "vit_checkpoint_read_momentum": (I, [ctypes.c_char_p, ctypes.POINTER(VitConfigC), P, P, ctypes.POINTER(LL),
+                                         ctypes.POINTER(I)]),
     # input pipeline (include/vit_data.h)
     "vit_loader_open": (P, [ctypes.c_char_p, ctypes.c_char_p, I, I, ctypes.c_ulonglong, I, I, I, I, I]),
     "vit_loader_num_records": (LL, [P]), "vit_loader_steps_per_epoch": (I, [P]),
@@ -248,6 +262,7 @@ HIT_LNB_MX = 90
 HIT_AUGMENT = 91  # + 0 statistics / LUT, 1 in-place apply, 2 out-of-place apply, 3 copy back
 HIT_EMA = 95  # a launch that advances an EMA of the weights (fused optimizer kernel or ema_update)
 HIT_ERASE = 96  # random erasing: one launch per call that has a non-empty box
+HIT_SGDM = 97  # momentum SGD: a momentum instantiation of the optimizer kernels or sgd_momentum_step
 
 
 def kernel_hits():
@@ -412,6 +427,14 @@ def lamb_step(p, g, m, v, n, lr, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=
          int(t), lamb_flags(always_adapt, trust_clip), info)
 
 
+def sgd_momentum_step(p, g, buf, n, lr, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False, first=False):
+    """One torch.optim.SGD momentum update of one tensor (the sgd_momentum_step op, include/vit_ops.h; the
+    statement is sgd.sgd_ref): p, g, buf are DeviceArrays or device addresses of n fp32 elements (any 4-byte
+    alignment); first=True seeds buf with the decayed gradient; synchronous."""
+    call("sgd_momentum_step", p, g, buf, int(n), float(lr), float(momentum), float(dampening), float(weight_decay),
+         int(bool(nesterov)), int(bool(first)))
+
+
 # --------------------------------------------------------------------------- checkpoints
 def checkpoint_info(path):
     """Header of a checkpoint file (include/vit_checkpoint.h) as a dict; host-only."""
@@ -427,14 +450,16 @@ def checkpoint_info(path):
 
 
 def write_checkpoint(path, cfg, params, m=None, v=None, step=0, adamw=None, ema=None, ema_decay=0.0,
-                     ema_updates=0):
+                     ema_updates=0, momentum=None, sgd=None, momentum_steps=0):
     """Write canonical fp32 params (+ AdamW m, v; + an EMA of the weights with its decay and update
-    count) in the checkpoint format; host-only.  Without `ema` the file is the one it always was."""
+    count; + a momentum-SGD buffer with its setting `sgd` = (momentum, dampening, weight_decay, nesterov) and
+    step count) in the checkpoint format; host-only.  Without `ema` and `momentum` the file is the one it
+    always was."""
     params = np.ascontiguousarray(params, dtype=np.float32)
     assert params.size == cfg.num_params()
     ptrs = [params.ctypes.data_as(P)]
     keep = []
-    for a in (m, v, ema):
+    for a in (m, v, ema, momentum):
         if a is None:
             ptrs.append(None)
         else:
@@ -444,7 +469,13 @@ def write_checkpoint(path, cfg, params, m=None, v=None, step=0, adamw=None, ema=
             ptrs.append(a.ctypes.data_as(P))
     hp = AdamWC(*adamw) if adamw is not None else None
     hp_ref = ctypes.byref(hp) if hp is not None else None
-    if ema is None:
+    if momentum is not None:
+        assert sgd is not None, "a momentum buffer needs its setting"
+        sg = SgdC(float(sgd[0]), float(sgd[1]), float(sgd[2]), int(bool(sgd[3])))
+        rc = lib().vit_checkpoint_write_sgd(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step),
+                                            hp_ref, ptrs[3], float(ema_decay), int(ema_updates), ptrs[4],
+                                            ctypes.byref(sg), int(momentum_steps))
+    elif ema is None:
         rc = lib().vit_checkpoint_write(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step), hp_ref)
     else:
         rc = lib().vit_checkpoint_write_ex(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step),
@@ -469,6 +500,24 @@ def read_checkpoint_ema(path, cfg):
         check("read_checkpoint_ema")
         raise VitError("read_checkpoint_ema failed")
     return e, float(d.value), int(u.value)
+
+
+def read_checkpoint_momentum(path, cfg):
+    """(buffer, (momentum, dampening, weight_decay, nesterov), steps) of a checkpoint written for cfg;
+    (None, (0.0, 0.0, 0.0, False), 0) for a file without a momentum buffer."""
+    sg, n, has = SgdC(), LL(), I()
+    c = _cfg_c(cfg)
+    if lib().vit_checkpoint_read_momentum(os.fsencode(path), ctypes.byref(c), None, ctypes.byref(sg), ctypes.byref(n),
+                                          ctypes.byref(has)):
+        check("read_checkpoint_momentum")
+        raise VitError("read_checkpoint_momentum failed")
+    if not has.value:
+        return None, (0.0, 0.0, 0.0, False), 0
+    b = np.empty(cfg.num_params(), np.float32)
+    if lib().vit_checkpoint_read_momentum(os.fsencode(path), ctypes.byref(c), b.ctypes.data_as(P), None, None, None):
+        check("read_checkpoint_momentum")
+        raise VitError("read_checkpoint_momentum failed")
+    return b, (float(sg.momentum), float(sg.dampening), float(sg.weight_decay), bool(sg.nesterov)), int(n.value)
 
 
 def read_checkpoint(path, cfg):
@@ -914,6 +963,32 @@ class ViT:
             yield self
         finally:
             self._ok(lib().vit_trainer_ema_weights(self.h, 0), "ema_weights")
+
+    # ---- momentum SGD (include/vit_trainer.h)
+    def set_sgd(self, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False):
+        """torch.optim.SGD's momentum, dampening, coupled weight decay and Nesterov for every later
+        optimizer_step / train_step (vit_trainer_set_sgd; see sgd.PRESETS for timm's `momentum` and `sgd`).
+        set_sgd(0, 0, 0, False) is plain SGD again; the buffer and its step count stay.  Raises on a bad
+        setting (nesterov without momentum or with dampening, weight decay without momentum, NaN, negative)
+        and leaves the previous one."""
+        self._ok(lib().vit_trainer_set_sgd(self.h, float(momentum), float(dampening), float(weight_decay),
+                                           int(bool(nesterov))), "set_sgd")
+
+    def sgd_info(self):
+        """{"momentum", "dampening", "weight_decay", "nesterov": the setting in force, "steps": momentum steps
+        since the buffer was seeded} (vit_trainer_get_sgd_info)."""
+        mu, da, wd, ne, n = F(), F(), F(), I(), LL()
+        self._ok(lib().vit_trainer_get_sgd_info(self.h, ctypes.byref(mu), ctypes.byref(da), ctypes.byref(wd),
+                                                ctypes.byref(ne), ctypes.byref(n)), "get_sgd_info")
+        return {"momentum": float(mu.value), "dampening": float(da.value), "weight_decay": float(wd.value),
+                "nesterov": bool(ne.value), "steps": int(n.value)}
+
+    def momentum(self):
+        """The momentum buffer, canonical order (vit_trainer_get_momentum; synchronous; raises before the
+        first momentum step)."""
+        out = np.empty(self.num_parameters, dtype=np.float32)
+        self._ok(lib().vit_trainer_get_momentum(self.h, out.ctypes.data_as(P)), "get_momentum")
+        return out
 
     def adamw_state(self):
         """(m, v, t) in canonical order."""

@@ -114,7 +114,8 @@ int vit_checkpoint_read_info(const char* path, vit_checkpoint_info_t* info) {
         set_error("checkpoint %s: seek failed", path);
         return 1;
     }
-    const long long want = VIT_CKPT_HEADER_BYTES + in.num_params * 4 * ((in.has_opt ? 3 : 1) + ((h[10] & 2) ? 1 : 0));
+    const long long want = VIT_CKPT_HEADER_BYTES +
+                           in.num_params * 4 * ((in.has_opt ? 3 : 1) + ((h[10] & 2) ? 1 : 0) + ((h[10] & 4) ? 1 : 0));
     const long long have = (long long)ftello(fh.f);
     if (have != want) {
         set_error("checkpoint %s: %lld bytes, expected %lld", path, have, want);
@@ -132,7 +133,16 @@ int vit_checkpoint_write(const char* path, const vit_config_t* cfg, const float*
 int vit_checkpoint_write_ex(const char* path, const vit_config_t* cfg, const float* params,
                             const float* m, const float* v, int step, const vit_adamw_t* adamw,
                             const float* ema, float ema_decay, long long ema_updates) {
-    if (!path || !cfg || !params || (!m) != (!v) || (ema && ema_updates < 0)) {
+    return vit_checkpoint_write_sgd(path, cfg, params, m, v, step, adamw, ema, ema_decay, ema_updates, nullptr,
+                                    nullptr, 0);
+}
+
+int vit_checkpoint_write_sgd(const char* path, const vit_config_t* cfg, const float* params,
+                             const float* m, const float* v, int step, const vit_adamw_t* adamw,
+                             const float* ema, float ema_decay, long long ema_updates,
+                             const float* momentum, const vit_sgd_t* sgd, long long momentum_steps) {
+    if (!path || !cfg || !params || (!m) != (!v) || (ema && ema_updates < 0) ||
+        (momentum && (!sgd || momentum_steps < 0))) {
         set_error("vit_checkpoint_write: bad arguments");
         return 1;
     }
@@ -153,7 +163,7 @@ int vit_checkpoint_write_ex(const char* path, const vit_config_t* cfg, const flo
     hdr[7] = cfg->img;
     hdr[8] = cfg->patch;
     hdr[9] = cfg->in_ch;
-    hdr[10] = (m ? 1 : 0) | (ema ? 2 : 0);
+    hdr[10] = (m ? 1 : 0) | (ema ? 2 : 0) | (momentum ? 4 : 0);
     hdr[11] = m ? step : 0;
     hdr[12] = (int32_t)(uint32_t)(n & 0xffffffffLL);
     hdr[13] = (int32_t)(uint32_t)(n >> 32);
@@ -168,6 +178,14 @@ int vit_checkpoint_write_ex(const char* path, const vit_config_t* cfg, const flo
         hdr[19] = (int32_t)(uint32_t)(ema_updates & 0xffffffffLL);
         hdr[20] = (int32_t)(uint32_t)(ema_updates >> 32);
     }
+    if (momentum) {
+        hdr[21] = (int32_t)(uint32_t)(momentum_steps & 0xffffffffLL);
+        hdr[22] = (int32_t)(uint32_t)(momentum_steps >> 32);
+        hdr[23] = (int32_t)fbits(sgd->momentum);
+        hdr[24] = (int32_t)fbits(sgd->dampening);
+        hdr[25] = (int32_t)fbits(sgd->weight_decay);
+        hdr[26] = sgd->nesterov ? 1 : 0;
+    }
     // write to path.tmp and rename, so an interrupted save never leaves a truncated checkpoint
     const std::string tmp = std::string(path) + ".tmp";
     {
@@ -180,6 +198,7 @@ int vit_checkpoint_write_ex(const char* path, const vit_config_t* cfg, const flo
                   write_all(fh.f, params, (size_t)n * 4);
         if (ok && m) ok = write_all(fh.f, m, (size_t)n * 4) && write_all(fh.f, v, (size_t)n * 4);
         if (ok && ema) ok = write_all(fh.f, ema, (size_t)n * 4);
+        if (ok && momentum) ok = write_all(fh.f, momentum, (size_t)n * 4);
         // durable before the rename: the data blocks must reach the disk before the new name does
         ok = ok && fflush(fh.f) == 0 && fsync(fileno(fh.f)) == 0;
         if (!ok) {
@@ -255,6 +274,38 @@ int vit_checkpoint_read_ema(const char* path, const vit_config_t* cfg, float* em
         const long long skip = VIT_CKPT_HEADER_BYTES + in.num_params * 4 * (in.has_opt ? 3 : 1);
         if (fseeko(fh.f, skip, SEEK_SET) != 0 || !read_all(fh.f, ema, (size_t)in.num_params * 4)) {
             set_error("checkpoint %s: short EMA section", path);
+            return 1;
+        }
+    }
+    return 0;
+}
+
+int vit_checkpoint_read_momentum(const char* path, const vit_config_t* cfg, float* momentum, vit_sgd_t* sgd,
+                                 long long* steps, int* has_momentum) {
+    vit_checkpoint_info_t in;
+    if (vit_checkpoint_read_info(path, &in)) return 1;  // (validates the size of every layout)
+    if (!cfg || memcmp(&in.cfg, cfg, sizeof(vit_config_t)) != 0) {
+        set_error("checkpoint %s: config differs from the model's", path);
+        return 1;
+    }
+    int32_t h[27];
+    File fh(fopen(path, "rb"));
+    if (!fh.f || !read_all(fh.f, h, sizeof(h))) {
+        set_error("checkpoint %s: short header", path);
+        return 1;
+    }
+    const bool has = (h[10] & 4) != 0;
+    if (has_momentum) *has_momentum = has ? 1 : 0;
+    if (sgd) {
+        *sgd = vit_sgd_t{0.f, 0.f, 0.f, 0};
+        if (has) *sgd = vit_sgd_t{bitsf((uint32_t)h[23]), bitsf((uint32_t)h[24]), bitsf((uint32_t)h[25]), h[26] != 0};
+    }
+    if (steps) *steps = has ? (long long)(uint32_t)h[21] | ((long long)(uint32_t)h[22] << 32) : 0;
+    if (has && momentum) {
+        const long long skip =
+            VIT_CKPT_HEADER_BYTES + in.num_params * 4 * ((in.has_opt ? 3 : 1) + ((h[10] & 2) ? 1 : 0));
+        if (fseeko(fh.f, skip, SEEK_SET) != 0 || !read_all(fh.f, momentum, (size_t)in.num_params * 4)) {
+            set_error("checkpoint %s: short momentum section", path);
             return 1;
         }
     }

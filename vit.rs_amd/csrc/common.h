@@ -224,6 +224,38 @@ __device__ __forceinline__ float adamw_update(float p, float g, float& m, float&
     return p - lr * adamw_moments(p, g, m, v, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
 }
 
+// Momentum SGD (torch.optim.SGD with momentum mu, dampening, Nesterov and coupled weight
+// decay): one element, every operation rounded to fp32 on its own (no contraction), g already clipped.
+//   g2 = wd != 0 ? g + wd * p : g          (torch skips the term at wd == 0; so does this)
+//   b' = first ? g2 : mu * b + omd * g2    (first: the step after the buffer was created or reset; torch's
+//                                           buf = grad.clone(): g2's bits, the old b not looked at)
+//   d  = nesterov ? g2 + mu * b' : b'
+//   p' = p - lr * d
+// omd = (float)(1.0 - (double)dampening), taken once on the host.  wd != 0, nesterov and first are
+// wave-uniform: of the launch or of the tile's segment.
+__device__ __forceinline__ float sgdm_update(float p, float g, float& b, float lr, float mu, float omd, float wd,
+                                             bool nesterov, bool first) {
+#pragma clang fp contract(off)
+    if (wd != 0.f) {
+        const float w = wd * p;
+        g = g + w;
+    }
+    float bn = g;
+    if (!first) {
+        const float x = mu * b;
+        const float y = omd * g;
+        bn = x + y;
+    }
+    b = bn;
+    float d = bn;
+    if (nesterov) {
+        const float x = mu * bn;
+        d = g + x;
+    }
+    const float s = lr * d;
+    return p - s;
+}
+
 // Parameter groups: per-(tensor, layer) multipliers of lr and weight decay inside
 // the fused optimizer kernels.  A segment is one placement of the arena layout with the alignment
 // padding behind it (starts are multiples of 64 elements); every segment is cut into tiles of
@@ -282,6 +314,18 @@ __device__ __forceinline__ void adamw_update4(float4& pv, float4 gv, float4& mv,
     pv.y = adamw_update(pv.y, gv.y, mv.y, vv.y, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
     pv.z = adamw_update(pv.z, gv.z, mv.z, vv.z, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
     pv.w = adamw_update(pv.w, gv.w, mv.w, vv.w, lr, b1, b2, omb1, omb2, bc1, bc2, eps, wd);
+}
+template <bool CLIP>
+__device__ __forceinline__ void sgdm_update4(float4& pv, float4 gv, float4& bv, float lr, float mu, float omd,
+                                             float wd, bool nesterov, bool first, float c) {
+    if (CLIP) {
+        gv.x = clip_scale(c, gv.x); gv.y = clip_scale(c, gv.y);
+        gv.z = clip_scale(c, gv.z); gv.w = clip_scale(c, gv.w);
+    }
+    pv.x = sgdm_update(pv.x, gv.x, bv.x, lr, mu, omd, wd, nesterov, first);
+    pv.y = sgdm_update(pv.y, gv.y, bv.y, lr, mu, omd, wd, nesterov, first);
+    pv.z = sgdm_update(pv.z, gv.z, bv.z, lr, mu, omd, wd, nesterov, first);
+    pv.w = sgdm_update(pv.w, gv.w, bv.w, lr, mu, omd, wd, nesterov, first);
 }
 
 // XCD-aware bijective remap of a linear workgroup id (cdna_hip_programming.md §5, "XCD swizzle

@@ -4,20 +4,23 @@
 #include "common.h"
 
 namespace vit {
-enum OptKind { OPT_SGD, OPT_ADAMW };
+enum OptKind { OPT_SGD, OPT_ADAMW, OPT_SGDM };
 
 struct OptimHp {
     float lr;
-    float b1, b2, omb1, omb2, bc1, bc2, eps, wd;  // AdamW only (common.h adamw_update)
+    float b1, b2, omb1, omb2, bc1, bc2, eps;  // AdamW only (common.h adamw_update)
+    float wd;                                 // AdamW and momentum SGD
+    float mu, omd;                            // momentum SGD only (common.h sgdm_update): momentum, 1 - dampening
+    int nesterov, first;                      // ... Nesterov's form; the buffer is seeded by this step
 };
 // One optimizer launch.  A flat range is the n elements from p / g / ... (n % 4 == 0, 16-byte aligned
 // pointers); a tiled range is the tiles [tile_begin, tile_begin + ntiles) of gt, with p / g / ... the
-// arena bases and lr (AdamW: and wd) multiplied per segment.
+// arena bases and lr (AdamW, momentum SGD: and wd) multiplied per segment.
 struct OptimArgs {
     float* p;
     bf16_t* pbf;         // the bf16 shadow of p; null = none
     const float* g;
-    float *m, *v;        // AdamW only
+    float *m, *v;        // AdamW's moments; momentum SGD: m is the momentum buffer, v unused
     OptimHp hp;
     const ClipRec* rec;  // null = unclipped
     EmaArg ema;          // e null = no EMA
@@ -29,8 +32,9 @@ struct OptimArgs {
 // the workgroups of a tiled launch over ntiles tiles (8 per CU, the rest grid-strided)
 int group_grid(int ntiles);
 // Launches the instantiation for (kind, tiled, a.rec, a.pbf, a.ema.e) on st; an empty range launches
-// nothing.  SGD without a shadow has no EMA instantiation (fp32 mode runs ema_update behind the step):
-// that combination is an error, as is a flat range that is not whole aligned float4s.
+// nothing.  Plain SGD without a shadow has no EMA instantiation (fp32 mode runs ema_update behind the step):
+// that combination is an error, as is a flat range that is not whole aligned float4s.  AdamW and momentum
+// SGD test the shadow at run time: their EMA instantiations serve fp32 mode too.
 void optimizer_launch(OptKind kind, const OptimArgs& a, bool tiled, hipStream_t st);
 
 // LAMB: AdamW's direction u scaled per segment by the trust ratio |w| / |u|, in three

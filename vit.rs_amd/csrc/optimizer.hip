@@ -1,6 +1,6 @@
-// optimizer.hip — SGD and AdamW over the parameter arena: one flat and one tiled body, each written
+// optimizer.hip — SGD, momentum SGD and AdamW over the parameter arena: one flat and one tiled body, each written
 // once over an update rule, and the launcher that picks the instantiation (optimizer.h).
-// The arithmetic is that of common.h (sgd_update, adamw_update, clip_scale, ema_blend, group_hp).
+// The arithmetic is that of common.h (sgd_update, sgdm_update, adamw_update, clip_scale, ema_blend, group_hp).
 // LAMB is three kernels of its own over the same tiles, behind the launcher's LambArgs form.
 #include "optimizer.h"
 
@@ -52,6 +52,28 @@ struct AdamwRule {
     template <bool CLIP>
     static __device__ __forceinline__ void update4(float4& pv, float4 gv, State& st, const OptimHp& hp, float c) {
         adamw_update4<CLIP>(pv, gv, st.m, st.v, hp.lr, hp.b1, hp.b2, hp.omb1, hp.omb2, hp.bc1, hp.bc2, hp.eps, hp.wd, c);
+    }
+};
+
+// Momentum SGD (torch.optim.SGD): the buffer b beside p (float4 i of m + at).  One pass:
+// reads p, g, b and writes p, b (+ pbf) = 5 x 4 B (+2 B) per parameter.  wd_e != 0, nesterov and first are
+// wave-uniform (hp comes from the kernel arguments and the segment's scalar loads).
+struct SgdmRule {
+    static constexpr bool NULLABLE_SHADOW = true;  // pbf tested at run time (fp32 mode has none)
+    struct State {
+        float4 b;
+    };
+    static __device__ __forceinline__ float4* state4(float* q, long long at) { return reinterpret_cast<float4*>(q + at); }
+    static __device__ __forceinline__ State load(const float4* b4, const float4*, long long i) { return State{b4[i]}; }
+    static __device__ __forceinline__ void store(float4* b4, float4*, long long i, const State& st) { b4[i] = st.b; }
+    static __device__ __forceinline__ OptimHp segment_hp(OptimHp hp, const GroupTab& gt, int seg) {
+        hp.lr = group_hp(hp.lr, gt.lr_mul[seg]);
+        hp.wd = group_hp(hp.wd, gt.wd_mul[seg]);
+        return hp;
+    }
+    template <bool CLIP>
+    static __device__ __forceinline__ void update4(float4& pv, float4 gv, State& st, const OptimHp& hp, float c) {
+        sgdm_update4<CLIP>(pv, gv, st.b, hp.lr, hp.mu, hp.omd, hp.wd, hp.nesterov != 0, hp.first != 0, c);
     }
 };
 
@@ -177,9 +199,27 @@ __global__ __launch_bounds__(GROUP_THREADS) void adamw_tiles_k(OptimArgs a) {
     tiles_body<AdamwRule, CLIP, false, EMA>(a.p, a.pbf, a.g, a.m, a.v, a.ema, a.gt, a.tile_begin, a.ntiles, a.hp,
                                             CLIP ? a.rec->c : 1.0f);
 }
+template <bool CLIP, bool EMA>
+__global__ void sgdm_flat_k(OptimArgs a) {
+    flat_body<SgdmRule, CLIP, false, EMA>(a.p, a.pbf, a.g, a.m, nullptr, a.ema, a.n / 4, a.hp, CLIP ? a.rec->c : 1.0f);
+}
+template <bool CLIP, bool EMA>
+__global__ __launch_bounds__(GROUP_THREADS) void sgdm_tiles_k(OptimArgs a) {
+    tiles_body<SgdmRule, CLIP, false, EMA>(a.p, a.pbf, a.g, a.m, nullptr, a.ema, a.gt, a.tile_begin, a.ntiles, a.hp,
+                                           CLIP ? a.rec->c : 1.0f);
+}
+// sgd_momentum_step (include/vit_ops.h): the scalar form, any n and any alignment
+__global__ void sgdm_scalar_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ b, long long n,
+                              OptimHp hp) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float bi = b[i];
+        p[i] = sgdm_update(p[i], g[i], bi, hp.lr, hp.mu, hp.omd, hp.wd, hp.nesterov != 0, hp.first != 0);
+        b[i] = bi;
+    }
+}
 
 // Every instantiation there is.  SGD: [tiled][CLIP][no shadow | shadow | shadow + EMA] (no shadow: fp32
-// mode, whose EMA is ema_update behind the step); AdamW: [tiled][CLIP][EMA].
+// mode, whose EMA is ema_update behind the step); AdamW and momentum SGD: [tiled][CLIP][EMA].
 using OptimKernel = void (*)(OptimArgs);
 const OptimKernel kSgd[2][2][3] = {
     {{sgd_flat_k<false, false, false>, sgd_flat_k<false, true, false>, sgd_flat_k<false, true, true>},
@@ -189,6 +229,9 @@ const OptimKernel kSgd[2][2][3] = {
 const OptimKernel kAdamw[2][2][2] = {
     {{adamw_flat_k<false, false>, adamw_flat_k<false, true>}, {adamw_flat_k<true, false>, adamw_flat_k<true, true>}},
     {{adamw_tiles_k<false, false>, adamw_tiles_k<false, true>}, {adamw_tiles_k<true, false>, adamw_tiles_k<true, true>}}};
+const OptimKernel kSgdm[2][2][2] = {
+    {{sgdm_flat_k<false, false>, sgdm_flat_k<false, true>}, {sgdm_flat_k<true, false>, sgdm_flat_k<true, true>}},
+    {{sgdm_tiles_k<false, false>, sgdm_tiles_k<false, true>}, {sgdm_tiles_k<true, false>, sgdm_tiles_k<true, true>}}};
 
 bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
@@ -471,23 +514,26 @@ const LambKernel kLambApply[2][2] = {{lamb_apply_tiles_k<false, false>, lamb_app
 int group_grid(int ntiles) { return ntiles < 2048 ? ntiles : 2048; }
 
 void optimizer_launch(OptKind kind, const OptimArgs& a, bool tiled, hipStream_t st) {
-    const bool adamw = kind == OPT_ADAMW, clip = a.rec != nullptr, shadow = a.pbf != nullptr, ema = a.ema.e != nullptr;
+    const bool adamw = kind == OPT_ADAMW, sgdm = kind == OPT_SGDM, clip = a.rec != nullptr, shadow = a.pbf != nullptr,
+               ema = a.ema.e != nullptr;
     char what[48];
-    snprintf(what, sizeof what, "%s_%s%s%s%s", adamw ? "adamw" : "sgd", tiled ? "tiles" : "flat", clip ? "_clip" : "",
-             shadow ? "_shadow" : "", ema ? "_ema" : "");
-    VIT_REQUIRE(adamw || shadow || !ema, "%s: SGD without a bf16 shadow has no fused EMA", what);
+    snprintf(what, sizeof what, "%s_%s%s%s%s", adamw ? "adamw" : sgdm ? "sgdm" : "sgd", tiled ? "tiles" : "flat",
+             clip ? "_clip" : "", shadow ? "_shadow" : "", ema ? "_ema" : "");
+    VIT_REQUIRE(adamw || sgdm || shadow || !ema, "%s: SGD without a bf16 shadow has no fused EMA", what);
+    VIT_REQUIRE(!sgdm || a.m, "%s: no momentum buffer", what);
     // (the flat bodies have no scalar tail: arena and chunk extents are multiples of 64 elements)
     VIT_REQUIRE(tiled || (a.n % 4 == 0 && aligned16(a.p) && aligned16(a.g) && aligned16(a.m) && aligned16(a.v) &&
                           aligned16(a.ema.e) && ((uintptr_t)a.pbf & 7) == 0),
                 "%s: a flat range must be whole 16-byte aligned float4s (n %lld)", what, a.n);
     if (tiled ? a.ntiles <= 0 : a.n <= 0) return;
-    const OptimKernel k = adamw ? kAdamw[tiled][clip][ema] : kSgd[tiled][clip][shadow + ema];
+    const OptimKernel k = adamw ? kAdamw[tiled][clip][ema] : sgdm ? kSgdm[tiled][clip][ema] : kSgd[tiled][clip][shadow + ema];
     if (tiled)
         k<<<group_grid(a.ntiles), GROUP_THREADS, 0, st>>>(a);
     else
         k<<<grid_for(a.n / 4, 256), 256, 0, st>>>(a);
     after_launch(what);
     if (ema) count_hit(VIT_HIT_EMA);
+    if (sgdm) count_hit(VIT_HIT_SGDM);
 }
 
 void optimizer_launch(const LambArgs& a, bool tiled, hipStream_t st) {
@@ -541,4 +587,29 @@ void lamb_step(float* p, const float* g, float* m, float* v, long long n, float 
     a.rec = info ? info : (float*)(ws + (size_t)ntiles * sizeof(double2));
     a.flags = flags;
     optimizer_launch(a, false, stream());
+}
+
+// (include/vit_ops.h) torch.optim.SGD's momentum update of one tensor: common.h sgdm_update per element
+void sgd_momentum_step(float* p, const float* g, float* buf, long long n, float lr, float momentum, float dampening,
+                       float weight_decay, int nesterov, int first) {
+    using namespace vit;
+    VIT_REQUIRE(n >= 0 && (n == 0 || (p && g && buf)), "sgd_momentum_step: n %lld or a null pointer", n);
+    VIT_REQUIRE(std::isfinite(lr) && std::isfinite(momentum) && momentum >= 0.f && std::isfinite(dampening) &&
+                    std::isfinite(weight_decay) && weight_decay >= 0.f,
+                "sgd_momentum_step: lr %g, momentum %g >= 0, dampening %g or weight_decay %g >= 0 is not finite",
+                (double)lr, (double)momentum, (double)dampening, (double)weight_decay);
+    VIT_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f),
+                "sgd_momentum_step: nesterov needs momentum > 0 and dampening 0 (momentum %g, dampening %g)",
+                (double)momentum, (double)dampening);
+    if (n == 0) return;
+    OptimHp hp{};
+    hp.lr = lr;
+    hp.wd = weight_decay;
+    hp.mu = momentum;
+    hp.omd = (float)(1.0 - (double)dampening);
+    hp.nesterov = nesterov != 0;
+    hp.first = first != 0;
+    sgdm_scalar_k<<<grid_for(n, 256), 256, 0, stream()>>>(p, g, buf, n, hp);
+    after_launch("sgd_momentum_step");
+    count_hit(VIT_HIT_SGDM);
 }

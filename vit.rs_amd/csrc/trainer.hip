@@ -1763,8 +1763,8 @@ struct Trainer {
     void sgd_chunk(int c) {
         chunk_fan_in(c);
         // the chunk's flat range, or its tiles of the whole-arena tiled kernel: elementwise, the one pass's bits
-        optimizer_launch(OPT_SGD, optim_args(c, early_lr, false), groups_on, s_comm);
-        if (!ema_fuse(false)) ema_behind(c, s_comm);
+        optimizer_launch(sgd_kind(), optim_args(c, early_lr, false), groups_on, s_comm);
+        if (!ema_fuse(sgdm_on())) ema_behind(c, s_comm);
     }
     // chunk c's gradients are final on s (and, in the bf16 / fp8 backward with concurrency on, on s2 and
     // ms[1..nmb)): s_comm waits for all of them.  early_on and clip_live each imply two_streams && lowp()
@@ -1956,9 +1956,10 @@ struct Trainer {
     long long ema_updates = 0;
     // option "ema_fused" (default 1): 0 launches the optimizer kernels without EMA and ema_update behind
     // each on the same stream (12 B per parameter instead of 8; the same bits): the A/B of
-    // tools/bench_ema.py.  fp32-mode SGD has no EMA instantiation (optimizer.hip) and always takes that form.
+    // tools/bench_ema.py.  fp32-mode plain SGD has no EMA instantiation (optimizer.hip) and always takes that
+    // form; AdamW and momentum SGD (shadowless = true) have one that needs no shadow.
     bool ema_fused = true;
-    bool ema_fuse(bool adamw) const { return ema_on && ema_fused && (lowp() || adamw); }
+    bool ema_fuse(bool shadowless) const { return ema_on && ema_fused && (lowp() || shadowless); }
     // the stand-alone update of gradient chunk c (c < 0: the whole arena) behind an un-fused optimizer launch
     void ema_behind(int c, hipStream_t st) {
         if (!ema_on) return;
@@ -2018,6 +2019,49 @@ struct Trainer {
         if (!ema_view) return true;
         set_error("%s: EMA weights in use", who);
         return false;
+    }
+
+    // Momentum SGD (vit_trainer_set_sgd): a setting of step / train_step / sgd_chunk.  While
+    // momentum > 0 they launch the OPT_SGDM kernels over sgd_buf (one fp32 arena in the layout of params,
+    // allocated and zeroed by the first such step), with first = 1 while sgd_steps == 0: the early per-chunk
+    // launches of a train_step see the count its step() then advances, so every chunk of one step agrees.
+    vit_sgd_t sgd_hp{0.f, 0.f, 0.f, 0};
+    float sgd_omd = 1.0f;  // (float)(1.0 - (double)dampening)
+    float* sgd_buf = nullptr;
+    long long sgd_steps = 0;
+    bool sgdm_on() const { return sgd_hp.momentum > 0.f; }
+    OptKind sgd_kind() const { return sgdm_on() ? OPT_SGDM : OPT_SGD; }
+    bool ensure_sgd_buf() {
+        if (sgd_buf) return true;
+        sgd_buf = alloc<float>(arena_elems);
+        if (!sgd_buf) return false;
+        VIT_HIP(hipMemsetAsync(sgd_buf, 0, arena_elems * 4, s));  // (s_comm's chunk launches wait for s: chunk_fan_in)
+        return true;
+    }
+    bool set_sgd(float mu, float damp, float wd, int nesterov) {
+        if (!sgd_valid(mu, damp, wd, nesterov)) return false;
+        sgd_hp = vit_sgd_t{mu, damp, wd, nesterov ? 1 : 0};
+        sgd_omd = (float)(1.0 - (double)damp);
+        return true;
+    }
+    // torch.optim.SGD's argument rules, and no decay without a buffer; false with the error set
+    static bool sgd_valid(float mu, float damp, float wd, int nesterov) {
+        if (!(std::isfinite(mu) && mu >= 0.f && std::isfinite(damp) && std::isfinite(wd) && wd >= 0.f)) {
+            set_error("vit_trainer_set_sgd: momentum %g / weight_decay %g is not finite and >= 0, or dampening %g is "
+                      "not finite", (double)mu, (double)wd, (double)damp);
+            return false;
+        }
+        if (nesterov && !(mu > 0.f && damp == 0.f)) {
+            set_error("vit_trainer_set_sgd: nesterov needs momentum > 0 and dampening 0 (momentum %g, dampening %g)",
+                      (double)mu, (double)damp);
+            return false;
+        }
+        if (wd > 0.f && !(mu > 0.f)) {
+            set_error("vit_trainer_set_sgd: weight_decay %g needs momentum > 0 (plain SGD has no decayed form)",
+                      (double)wd);
+            return false;
+        }
+        return true;
     }
 
     bool ensure_adam() {
@@ -2214,7 +2258,7 @@ struct Trainer {
     // The arguments of the optimizer launch over gradient chunk c (c < 0: the whole arena) from the
     // trainer's state: the chunk's tiles of the arena with parameter groups on, its flat range otherwise.
     // rec is the record clip_norm() has written (the caller runs it first); m / v and the AdamW
-    // hyper-parameters are the caller's.
+    // hyper-parameters are the caller's; an SGD launch with momentum on gets the buffer and its setting here.
     OptimArgs optim_args(int c, float lr, bool adamw) const {
         const long long o = c < 0 || groups_on ? 0 : chunk_off[c];
         OptimArgs a{};
@@ -2223,7 +2267,15 @@ struct Trainer {
         if (lowp()) a.pbf = pbf + o;
         a.hp.lr = lr;
         if (clip_on()) a.rec = clip_rec;
-        if (ema_fuse(adamw)) a.ema = EmaArg{ema + o, ema_d, ema_omd};
+        if (ema_fuse(adamw || sgdm_on())) a.ema = EmaArg{ema + o, ema_d, ema_omd};
+        if (!adamw && sgdm_on()) {
+            a.m = sgd_buf + o;
+            a.hp.wd = sgd_hp.weight_decay;
+            a.hp.mu = sgd_hp.momentum;
+            a.hp.omd = sgd_omd;
+            a.hp.nesterov = sgd_hp.nesterov;
+            a.hp.first = sgd_steps == 0;
+        }
         if (groups_on) {
             a.gt = grp_tab;
             a.tile_begin = c < 0 ? 0 : grp_chunk_tile[c];
@@ -2241,14 +2293,17 @@ struct Trainer {
             early_done = false;
             VIT_HIP(hipEventRecord(comm_done, s_comm));
             VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
+            if (sgdm_on()) sgd_steps++;
             refresh_transposed();
             return;
         }
         finish_allreduce();
+        if (sgdm_on() && !ensure_sgd_buf()) return;
         tbeg(TC_SGD, 0);
         if (clip_on()) clip_norm();
-        optimizer_launch(OPT_SGD, optim_args(-1, lr, false), groups_on, s);
-        if (!ema_fuse(false)) ema_behind(-1, s);
+        optimizer_launch(sgd_kind(), optim_args(-1, lr, false), groups_on, s);
+        if (sgdm_on()) sgd_steps++;
+        if (!ema_fuse(sgdm_on())) ema_behind(-1, s);
         tend();
         if (lowp()) refresh_transposed();
     }
@@ -2567,6 +2622,7 @@ int vit_trainer_train_step(vit_trainer_t* h, float lr, int b_global) {
     t.early_on = t.early_sgd_on() && t.lowp() && !t.comm && t.two_streams && !t.timing && t.s2 && t.has_targets &&
                  !t.clip_on();
     t.early_lr = lr;
+    if (t.early_on && t.sgdm_on() && !t.ensure_sgd_buf()) t.early_on = false;  // (the error is set: step() reports it)
     vit_trainer_backward(h);
     t.early_done = t.early_on && !vit::has_error();
     t.early_on = false;
@@ -2737,6 +2793,37 @@ int vit_trainer_ema_weights(vit_trainer_t* h, int on) {
     }
     return h->t.ema_weights(on != 0) ? 0 : 1;
 }
+int vit_trainer_set_sgd(vit_trainer_t* h, float momentum, float dampening, float weight_decay, int nesterov) {
+    if (!h) {
+        set_error("vit_trainer_set_sgd: null trainer");
+        return 1;
+    }
+    if (!h->t.ema_unlocked("vit_trainer_set_sgd")) return 1;
+    return h->t.set_sgd(momentum, dampening, weight_decay, nesterov) ? 0 : 1;
+}
+int vit_trainer_get_sgd_info(vit_trainer_t* h, float* momentum, float* dampening, float* weight_decay, int* nesterov,
+                             long long* steps) {
+    if (!h) {
+        set_error("vit_trainer_get_sgd_info: null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    if (momentum) *momentum = t.sgd_hp.momentum;
+    if (dampening) *dampening = t.sgd_hp.dampening;
+    if (weight_decay) *weight_decay = t.sgd_hp.weight_decay;
+    if (nesterov) *nesterov = t.sgd_hp.nesterov;
+    if (steps) *steps = t.sgd_steps;
+    return 0;
+}
+int vit_trainer_get_momentum(vit_trainer_t* h, float* host) {
+    if (!h || !host || !h->t.sgd_buf || !h->t.sgd_steps) {
+        set_error("vit_trainer_get_momentum: %s", !h || !host ? "null argument" : "no momentum step has run");
+        return 1;
+    }
+    VIT_HIP(hipDeviceSynchronize());
+    h->t.device_to_canon(h->t.sgd_buf, host);
+    return vit::has_error();
+}
 int vit_trainer_get_adamw_state(vit_trainer_t* h, float* m, float* v, int* step) {
     auto& t = h->t;
     if (step) *step = t.adam_t;
@@ -2774,6 +2861,25 @@ int vit_trainer_save_checkpoint(vit_trainer_t* h, const char* path) {
     if (vit::has_error()) return 1;
     std::vector<float> p((size_t)t.n_params), m, v;
     t.device_to_canon(t.params, p.data());
+    if (t.sgd_buf && t.sgd_steps) {  // a momentum step has run: every section that exists, the buffer last
+        std::vector<float> e, b((size_t)t.n_params);
+        t.device_to_canon(t.sgd_buf, b.data());
+        if (t.ema_on) {
+            e.resize((size_t)t.n_params);
+            t.device_to_canon(t.ema, e.data());
+        }
+        if (t.adam_m) {
+            m.resize((size_t)t.n_params);
+            v.resize((size_t)t.n_params);
+            t.device_to_canon(t.adam_m, m.data());
+            t.device_to_canon(t.adam_v, v.data());
+        }
+        if (vit::has_error()) return 1;
+        return vit_checkpoint_write_sgd(path, &t.cfg, p.data(), t.adam_m ? m.data() : nullptr,
+                                        t.adam_m ? v.data() : nullptr, t.adam_t, &t.adam_hp,
+                                        t.ema_on ? e.data() : nullptr, t.ema_d, t.ema_updates, b.data(), &t.sgd_hp,
+                                        t.sgd_steps);
+    }
     if (t.ema_on) {  // (a trainer with EMA off writes the file through the call it always used)
         std::vector<float> e((size_t)t.n_params);
         t.device_to_canon(t.ema, e.data());
@@ -2816,6 +2922,19 @@ int vit_trainer_load_checkpoint(vit_trainer_t* h, const char* path) {
         e.resize((size_t)t.n_params);
         if (vit_checkpoint_read_ema(path, &t.cfg, e.data(), nullptr, nullptr, nullptr)) return 1;
     }
+    std::vector<float> b;
+    vit_sgd_t b_hp{0.f, 0.f, 0.f, 0};
+    long long b_steps = 0;
+    int has_mom = 0;
+    if (vit_checkpoint_read_momentum(path, &t.cfg, nullptr, &b_hp, &b_steps, &has_mom)) return 1;
+    if (has_mom) {
+        if (b_steps < 0 || !vit::Trainer::sgd_valid(b_hp.momentum, b_hp.dampening, b_hp.weight_decay, b_hp.nesterov)) {
+            set_error("checkpoint %s: invalid momentum-SGD setting in the header", path);
+            return 1;
+        }
+        b.resize((size_t)t.n_params);
+        if (vit_checkpoint_read_momentum(path, &t.cfg, b.data(), nullptr, nullptr, nullptr)) return 1;
+    }
     if (info.has_opt) {
         m.resize((size_t)t.n_params);
         v.resize((size_t)t.n_params);
@@ -2836,6 +2955,14 @@ int vit_trainer_load_checkpoint(vit_trainer_t* h, const char* path) {
         VIT_HIP(hipMemsetAsync(t.adam_m, 0, t.arena_elems * 4, t.s));
         VIT_HIP(hipMemsetAsync(t.adam_v, 0, t.arena_elems * 4, t.s));
         t.adam_t = 0;
+    }
+    if (has_mom) {  // the file's buffer, count and setting
+        if (!t.ensure_sgd_buf()) return 1;
+        t.canon_to_device(b.data(), t.sgd_buf);
+        t.sgd_steps = b_steps;
+        t.set_sgd(b_hp.momentum, b_hp.dampening, b_hp.weight_decay, b_hp.nesterov);
+    } else {  // a file without one: the next momentum step seeds the buffer again; the setting stays
+        t.sgd_steps = 0;
     }
     if (has_ema) {  // the file's average, decay and count; EMA on
         if (!t.ema && !(t.ema = t.alloc<float>(t.arena_elems))) return 1;
