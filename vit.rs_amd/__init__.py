@@ -469,17 +469,14 @@ def write_checkpoint(path, cfg, params, m=None, v=None, step=0, adamw=None, ema=
             ptrs.append(a.ctypes.data_as(P))
     hp = AdamWC(*adamw) if adamw is not None else None
     hp_ref = ctypes.byref(hp) if hp is not None else None
+    sg = None
     if momentum is not None:
         assert sgd is not None, "a momentum buffer needs its setting"
         sg = SgdC(float(sgd[0]), float(sgd[1]), float(sgd[2]), int(bool(sgd[3])))
-        rc = lib().vit_checkpoint_write_sgd(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step),
-                                            hp_ref, ptrs[3], float(ema_decay), int(ema_updates), ptrs[4],
-                                            ctypes.byref(sg), int(momentum_steps))
-    elif ema is None:
-        rc = lib().vit_checkpoint_write(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step), hp_ref)
-    else:
-        rc = lib().vit_checkpoint_write_ex(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step),
-                                           hp_ref, ptrs[3], float(ema_decay), int(ema_updates))
+    # (NULL ema / momentum: the C side writes the bytes of the older layouts)
+    rc = lib().vit_checkpoint_write_sgd(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), *ptrs[:3], int(step), hp_ref,
+                                        ptrs[3], float(ema_decay), int(ema_updates), ptrs[4],
+                                        ctypes.byref(sg) if sg is not None else None, int(momentum_steps))
     if rc:
         check("write_checkpoint")
         raise VitError("write_checkpoint failed")
@@ -488,36 +485,26 @@ def write_checkpoint(path, cfg, params, m=None, v=None, step=0, adamw=None, ema=
 def read_checkpoint_ema(path, cfg):
     """(ema, decay, updates) of a checkpoint written for cfg; (None, 0.0, 0) for a file without an EMA."""
     d, u, has = F(), LL(), I()
-    c = _cfg_c(cfg)
-    if lib().vit_checkpoint_read_ema(os.fsencode(path), ctypes.byref(c), None, ctypes.byref(d), ctypes.byref(u),
-                                     ctypes.byref(has)):
+    e = np.empty(cfg.num_params(), np.float32)  # (left alone by a file without the section)
+    if lib().vit_checkpoint_read_ema(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), e.ctypes.data_as(P),
+                                     ctypes.byref(d), ctypes.byref(u), ctypes.byref(has)):
         check("read_checkpoint_ema")
         raise VitError("read_checkpoint_ema failed")
-    if not has.value:
-        return None, 0.0, 0
-    e = np.empty(cfg.num_params(), np.float32)
-    if lib().vit_checkpoint_read_ema(os.fsencode(path), ctypes.byref(c), e.ctypes.data_as(P), None, None, None):
-        check("read_checkpoint_ema")
-        raise VitError("read_checkpoint_ema failed")
-    return e, float(d.value), int(u.value)
+    return (e, float(d.value), int(u.value)) if has.value else (None, 0.0, 0)
 
 
 def read_checkpoint_momentum(path, cfg):
     """(buffer, (momentum, dampening, weight_decay, nesterov), steps) of a checkpoint written for cfg;
     (None, (0.0, 0.0, 0.0, False), 0) for a file without a momentum buffer."""
     sg, n, has = SgdC(), LL(), I()
-    c = _cfg_c(cfg)
-    if lib().vit_checkpoint_read_momentum(os.fsencode(path), ctypes.byref(c), None, ctypes.byref(sg), ctypes.byref(n),
-                                          ctypes.byref(has)):
-        check("read_checkpoint_momentum")
-        raise VitError("read_checkpoint_momentum failed")
-    if not has.value:
-        return None, (0.0, 0.0, 0.0, False), 0
     b = np.empty(cfg.num_params(), np.float32)
-    if lib().vit_checkpoint_read_momentum(os.fsencode(path), ctypes.byref(c), b.ctypes.data_as(P), None, None, None):
+    if lib().vit_checkpoint_read_momentum(os.fsencode(path), ctypes.byref(_cfg_c(cfg)), b.ctypes.data_as(P),
+                                          ctypes.byref(sg), ctypes.byref(n), ctypes.byref(has)):
         check("read_checkpoint_momentum")
         raise VitError("read_checkpoint_momentum failed")
-    return b, (float(sg.momentum), float(sg.dampening), float(sg.weight_decay), bool(sg.nesterov)), int(n.value)
+    # (without the section the C side reports an all-zero setting and count 0)
+    return (b if has.value else None, (float(sg.momentum), float(sg.dampening), float(sg.weight_decay),
+                                       bool(sg.nesterov)), int(n.value))
 
 
 def read_checkpoint(path, cfg):

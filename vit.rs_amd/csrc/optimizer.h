@@ -1,6 +1,7 @@
 // optimizer.h — the optimizer kernels of the trainer behind one parameter block and one launcher
 // (optimizer.hip; the matrix of instantiations is in DESIGN.md §16).
 #pragma once
+#include "../../include/vit_checkpoint.h"  // vit_adamw_t
 #include "common.h"
 
 namespace vit {
@@ -13,6 +14,9 @@ struct OptimHp {
     float mu, omd;                            // momentum SGD only (common.h sgdm_update): momentum, 1 - dampening
     int nesterov, first;                      // ... Nesterov's form; the buffer is seeded by this step
 };
+// AdamW's / LAMB's hyper-parameters of update t >= 1: 1 - beta and the bias corrections as the oracle rounds
+// them (pow in double, the result to fp32, 1.0f - that)
+OptimHp adamw_hp(float lr, const vit_adamw_t& hp, int t);
 // One optimizer launch.  A flat range is the n elements from p / g / ... (n % 4 == 0, 16-byte aligned
 // pointers); a tiled range is the tiles [tile_begin, tile_begin + ntiles) of gt, with p / g / ... the
 // arena bases and lr (AdamW, momentum SGD: and wd) multiplied per segment.

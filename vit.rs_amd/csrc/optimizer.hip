@@ -513,6 +513,12 @@ const LambKernel kLambApply[2][2] = {{lamb_apply_tiles_k<false, false>, lamb_app
 
 int group_grid(int ntiles) { return ntiles < 2048 ? ntiles : 2048; }
 
+OptimHp adamw_hp(float lr, const vit_adamw_t& hp, int t) {
+    const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)t);
+    const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)t);
+    return OptimHp{lr, hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay};
+}
+
 void optimizer_launch(OptKind kind, const OptimArgs& a, bool tiled, hipStream_t st) {
     const bool adamw = kind == OPT_ADAMW, sgdm = kind == OPT_SGDM, clip = a.rec != nullptr, shadow = a.pbf != nullptr,
                ema = a.ema.e != nullptr;
@@ -580,9 +586,7 @@ void lamb_step(float* p, const float* g, float* m, float* v, long long n, float 
     a.o.m = m;
     a.o.v = v;
     a.o.n = n;
-    // bias corrections and 1-beta exactly as the oracle rounds them (pow in double -> fp32)
-    a.o.hp = OptimHp{lr, beta1, beta2, 1.0f - beta1, 1.0f - beta2, 1.0f - (float)pow((double)beta1, (double)t),
-                     1.0f - (float)pow((double)beta2, (double)t), eps, weight_decay};
+    a.o.hp = adamw_hp(lr, vit_adamw_t{beta1, beta2, eps, weight_decay}, t);
     a.slots = (double2*)ws;
     a.rec = info ? info : (float*)(ws + (size_t)ntiles * sizeof(double2));
     a.flags = flags;

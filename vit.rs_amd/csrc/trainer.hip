@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "augment.h"
+#include "checkpoint_internal.h"
 #include "erase.h"
 #include "ops_internal.h"
 #include "optimizer.h"
@@ -1763,7 +1764,7 @@ struct Trainer {
     void sgd_chunk(int c) {
         chunk_fan_in(c);
         // the chunk's flat range, or its tiles of the whole-arena tiled kernel: elementwise, the one pass's bits
-        optimizer_launch(sgd_kind(), optim_args(c, early_lr, false), groups_on, s_comm);
+        optimizer_launch(sgd_kind(), optim_args(c, early_lr, false, groups_on), groups_on, s_comm);
         if (!ema_fuse(sgdm_on())) ema_behind(c, s_comm);
     }
     // chunk c's gradients are final on s (and, in the bf16 / fp8 backward with concurrency on, on s2 and
@@ -1978,8 +1979,7 @@ struct Trainer {
     }
     // the average := the current parameters (device copy), count 0
     bool ema_seed() {
-        if (!ema) ema = alloc<float>(arena_elems);
-        if (!ema) return false;
+        if (!ensure_arena(ema, false)) return false;
         ema_join();
         VIT_HIP(hipMemcpyAsync(ema, params, (size_t)arena_elems * 4, hipMemcpyDeviceToDevice, s));
         VIT_HIP(hipStreamSynchronize(s));
@@ -2031,13 +2031,8 @@ struct Trainer {
     long long sgd_steps = 0;
     bool sgdm_on() const { return sgd_hp.momentum > 0.f; }
     OptKind sgd_kind() const { return sgdm_on() ? OPT_SGDM : OPT_SGD; }
-    bool ensure_sgd_buf() {
-        if (sgd_buf) return true;
-        sgd_buf = alloc<float>(arena_elems);
-        if (!sgd_buf) return false;
-        VIT_HIP(hipMemsetAsync(sgd_buf, 0, arena_elems * 4, s));  // (s_comm's chunk launches wait for s: chunk_fan_in)
-        return true;
-    }
+    // (cleared on s; s_comm's chunk launches wait for s: chunk_fan_in)
+    bool ensure_sgd_buf() { return ensure_arena(sgd_buf, true); }
     bool set_sgd(float mu, float damp, float wd, int nesterov) {
         if (!sgd_valid(mu, damp, wd, nesterov)) return false;
         sgd_hp = vit_sgd_t{mu, damp, wd, nesterov ? 1 : 0};
@@ -2064,15 +2059,16 @@ struct Trainer {
         return true;
     }
 
-    bool ensure_adam() {
-        if (adam_m) return true;
-        adam_m = alloc<float>(arena_elems);
-        adam_v = alloc<float>(arena_elems);
-        if (!adam_m || !adam_v) return false;
-        VIT_HIP(hipMemsetAsync(adam_m, 0, arena_elems * 4, s));
-        VIT_HIP(hipMemsetAsync(adam_v, 0, arena_elems * 4, s));
+    // An optional fp32 arena in the layout of params (adam_m, adam_v, sgd_buf, ema): allocated on first use
+    // and, zero, cleared on s then.  false with the error set when the allocation fails.
+    bool ensure_arena(float*& a, bool zero) {
+        if (a) return true;
+        a = alloc<float>(arena_elems);
+        if (!a) return false;
+        if (zero) VIT_HIP(hipMemsetAsync(a, 0, arena_elems * 4, s));
         return true;
     }
+    bool ensure_adam() { return ensure_arena(adam_m, true) && ensure_arena(adam_v, true); }
     // Parameter groups (vit_trainer_set_param_groups): per-(tensor, layer) multipliers
     // of lr and weight decay.  grp_lr / grp_wd keep the setting in the canonical [20 * L] indexing
     // (ignored entries as 1); the device tables are per segment in arena order (common.h GroupTab).
@@ -2165,25 +2161,11 @@ struct Trainer {
     // AdamW update t = adam_t + 1 (llm.c's update, which the reference's m/v buffers —
     // train_vit.rs:73-74 — were allocated for; its optimizer_step :737 is SGD)
     void step_adamw(float lr, const vit_adamw_t& hp) {
-        pre_side_wait();
-        finish_allreduce();
-        if (!ensure_adam()) return;
-        adam_t += 1;
-        adam_hp = hp;
-        if (ema_on) ema_updates++;
-        // bias corrections and 1-beta exactly as the oracle rounds them (pow in double -> fp32)
-        const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)adam_t);
-        const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)adam_t);
-        tbeg(TC_SGD, 0);
-        if (clip_on()) clip_norm();
-        OptimArgs a = optim_args(-1, lr, true);
-        a.m = adam_m;
-        a.v = adam_v;
-        a.hp = OptimHp{lr, hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay};
+        if (!step_begin(&hp, false)) return;
+        OptimArgs a = optim_args(-1, lr, true, groups_on);
+        a.hp = adamw_hp(lr, hp, adam_t);
         optimizer_launch(OPT_ADAMW, a, groups_on, s);
-        if (!ema_fuse(true)) ema_behind(-1, s);
-        tend();
-        if (lowp()) refresh_transposed();
+        step_finish(true);
     }
     // LAMB (vit_trainer_step_lamb): AdamW's state and direction, the step of every segment
     // scaled by its trust ratio.  Always the tiled range of the parameter-group tables (a ratio is per
@@ -2217,50 +2199,58 @@ struct Trainer {
         return true;
     }
     void step_lamb(float lr, const vit_adamw_t& hp, int flags) {
-        pre_side_wait();
-        finish_allreduce();
-        if (!ensure_adam() || !lamb_enable()) return;
-        if (!groups_on && !grp_dev_ones) {  // the bits of 1.0f into both tables, on the device
-            VIT_HIP(hipMemsetD32Async((hipDeviceptr_t)grp_dev_lr, 0x3f800000, grp_tab.nseg, s));
-            VIT_HIP(hipMemsetD32Async((hipDeviceptr_t)grp_dev_wd, 0x3f800000, grp_tab.nseg, s));
-            grp_dev_ones = true;
-        }
-        adam_t += 1;
-        adam_hp = hp;
+        if (!step_begin(&hp, true)) return;
         lamb_steps += 1;
-        if (ema_on) ema_updates++;
-        const float bc1 = 1.0f - (float)pow((double)hp.beta1, (double)adam_t);
-        const float bc2 = 1.0f - (float)pow((double)hp.beta2, (double)adam_t);
-        tbeg(TC_SGD, 0);
-        if (clip_on()) clip_norm();
         LambArgs a{};
-        a.o.p = params;
-        a.o.g = grads;
-        if (lowp()) a.o.pbf = pbf;
-        a.o.m = adam_m;
-        a.o.v = adam_v;
-        a.o.hp = OptimHp{lr, hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, bc1, bc2, hp.eps, hp.weight_decay};
-        if (clip_on()) a.o.rec = clip_rec;
-        if (ema_fuse(true)) a.o.ema = EmaArg{ema, ema_d, ema_omd};
-        a.o.gt = grp_tab;
-        a.o.tile_begin = 0;
-        a.o.ntiles = grp_chunk_tile[n_chunks];
+        a.o = optim_args(-1, lr, true, true);
+        a.o.hp = adamw_hp(lr, hp, adam_t);
         a.seg_len = lamb_len;
         a.slots = lamb_slots;
         a.rec = lamb_rec;
         a.flags = flags;
         optimizer_launch(a, true, s);
-        if (!ema_fuse(true)) ema_behind(-1, s);
+        step_finish(true);
+    }
+
+    // What step, step_adamw (hp) and step_lamb (hp, lamb) share.  The begin: s behind the side streams and the
+    // all-reduce, the optimizer state of the step allocated (false, with the error set, if it cannot be), for
+    // AdamW / LAMB the counters advanced, then the clip record when clipping is on.  The finish: the EMA behind
+    // an optimizer launch that did not fuse it (shadowless: the launch has an EMA form without a bf16 shadow),
+    // and the transposed bf16 weights.
+    bool step_begin(const vit_adamw_t* hp, bool lamb) {
+        pre_side_wait();
+        finish_allreduce();
+        if (hp ? !ensure_adam() : (sgdm_on() && !ensure_sgd_buf())) return false;
+        if (lamb) {
+            if (!lamb_enable()) return false;
+            if (!groups_on && !grp_dev_ones) {  // the bits of 1.0f into both tables, on the device
+                VIT_HIP(hipMemsetD32Async((hipDeviceptr_t)grp_dev_lr, 0x3f800000, grp_tab.nseg, s));
+                VIT_HIP(hipMemsetD32Async((hipDeviceptr_t)grp_dev_wd, 0x3f800000, grp_tab.nseg, s));
+                grp_dev_ones = true;
+            }
+        }
+        if (hp) {
+            adam_t += 1;
+            adam_hp = *hp;
+            if (ema_on) ema_updates++;
+        }
+        tbeg(TC_SGD, 0);
+        if (clip_on()) clip_norm();
+        return true;
+    }
+    void step_finish(bool shadowless) {
+        if (!ema_fuse(shadowless)) ema_behind(-1, s);
         tend();
         if (lowp()) refresh_transposed();
     }
 
     // The arguments of the optimizer launch over gradient chunk c (c < 0: the whole arena) from the
-    // trainer's state: the chunk's tiles of the arena with parameter groups on, its flat range otherwise.
-    // rec is the record clip_norm() has written (the caller runs it first); m / v and the AdamW
-    // hyper-parameters are the caller's; an SGD launch with momentum on gets the buffer and its setting here.
-    OptimArgs optim_args(int c, float lr, bool adamw) const {
-        const long long o = c < 0 || groups_on ? 0 : chunk_off[c];
+    // trainer's state: tiled, the chunk's tiles of the arena (the form of parameter groups, and LAMB's
+    // always); its flat range otherwise.  rec is the record clip_norm() has written (the caller runs it
+    // first).  adamw: m / v are the moments, the hyper-parameters the caller's (adamw_hp); otherwise an SGD
+    // launch, which with momentum on gets the buffer and its setting here.
+    OptimArgs optim_args(int c, float lr, bool adamw, bool tiled) const {
+        const long long o = c < 0 || tiled ? 0 : chunk_off[c];
         OptimArgs a{};
         a.p = params + o;
         a.g = grads + o;
@@ -2268,7 +2258,10 @@ struct Trainer {
         a.hp.lr = lr;
         if (clip_on()) a.rec = clip_rec;
         if (ema_fuse(adamw || sgdm_on())) a.ema = EmaArg{ema + o, ema_d, ema_omd};
-        if (!adamw && sgdm_on()) {
+        if (adamw) {
+            a.m = adam_m + o;
+            a.v = adam_v + o;
+        } else if (sgdm_on()) {
             a.m = sgd_buf + o;
             a.hp.wd = sgd_hp.weight_decay;
             a.hp.mu = sgd_hp.momentum;
@@ -2276,7 +2269,7 @@ struct Trainer {
             a.hp.nesterov = sgd_hp.nesterov;
             a.hp.first = sgd_steps == 0;
         }
-        if (groups_on) {
+        if (tiled) {
             a.gt = grp_tab;
             a.tile_begin = c < 0 ? 0 : grp_chunk_tile[c];
             a.ntiles = grp_chunk_tile[c < 0 ? n_chunks : c + 1] - a.tile_begin;
@@ -2287,25 +2280,20 @@ struct Trainer {
     }
 
     void step(float lr) {
-        pre_side_wait();
         if (ema_on) ema_updates++;
         if (early_done) {  // every chunk already updated on s_comm (train_step with early SGD)
             early_done = false;
+            pre_side_wait();
             VIT_HIP(hipEventRecord(comm_done, s_comm));
             VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
             if (sgdm_on()) sgd_steps++;
             refresh_transposed();
             return;
         }
-        finish_allreduce();
-        if (sgdm_on() && !ensure_sgd_buf()) return;
-        tbeg(TC_SGD, 0);
-        if (clip_on()) clip_norm();
-        optimizer_launch(sgd_kind(), optim_args(-1, lr, false), groups_on, s);
+        if (!step_begin(nullptr, false)) return;
+        optimizer_launch(sgd_kind(), optim_args(-1, lr, false, groups_on), groups_on, s);
         if (sgdm_on()) sgd_steps++;
-        if (!ema_fuse(sgdm_on())) ema_behind(-1, s);
-        tend();
-        if (lowp()) refresh_transposed();
+        step_finish(sgdm_on());
     }
 };
 
@@ -2854,121 +2842,88 @@ int vit_trainer_eval(vit_trainer_t* h, int* host_pred, int* host_correct) {
     if (host_correct && t.has_targets) *host_correct = out[t.B];
     return 0;
 }
+// Save and load go through the one writer and the one reader of checkpoint.cpp: a section per optional
+// arena.
 int vit_trainer_save_checkpoint(vit_trainer_t* h, const char* path) {
+    using namespace vit::ckpt;
     auto& t = h->t;
     if (!t.ema_unlocked("vit_trainer_save_checkpoint")) return 1;
     VIT_HIP(hipDeviceSynchronize());
     if (vit::has_error()) return 1;
-    std::vector<float> p((size_t)t.n_params), m, v;
-    t.device_to_canon(t.params, p.data());
-    if (t.sgd_buf && t.sgd_steps) {  // a momentum step has run: every section that exists, the buffer last
-        std::vector<float> e, b((size_t)t.n_params);
-        t.device_to_canon(t.sgd_buf, b.data());
-        if (t.ema_on) {
-            e.resize((size_t)t.n_params);
-            t.device_to_canon(t.ema, e.data());
-        }
-        if (t.adam_m) {
-            m.resize((size_t)t.n_params);
-            v.resize((size_t)t.n_params);
-            t.device_to_canon(t.adam_m, m.data());
-            t.device_to_canon(t.adam_v, v.data());
-        }
-        if (vit::has_error()) return 1;
-        return vit_checkpoint_write_sgd(path, &t.cfg, p.data(), t.adam_m ? m.data() : nullptr,
-                                        t.adam_m ? v.data() : nullptr, t.adam_t, &t.adam_hp,
-                                        t.ema_on ? e.data() : nullptr, t.ema_d, t.ema_updates, b.data(), &t.sgd_hp,
-                                        t.sgd_steps);
-    }
-    if (t.ema_on) {  // (a trainer with EMA off writes the file through the call it always used)
-        std::vector<float> e((size_t)t.n_params);
-        t.device_to_canon(t.ema, e.data());
-        if (t.adam_m) {
-            m.resize((size_t)t.n_params);
-            v.resize((size_t)t.n_params);
-            t.device_to_canon(t.adam_m, m.data());
-            t.device_to_canon(t.adam_v, v.data());
-        }
-        if (vit::has_error()) return 1;
-        return vit_checkpoint_write_ex(path, &t.cfg, p.data(), t.adam_m ? m.data() : nullptr,
-                                       t.adam_m ? v.data() : nullptr, t.adam_t, &t.adam_hp, e.data(), t.ema_d,
-                                       t.ema_updates);
-    }
-    if (t.adam_m) {
-        m.resize((size_t)t.n_params);
-        v.resize((size_t)t.n_params);
-        t.device_to_canon(t.adam_m, m.data());
-        t.device_to_canon(t.adam_v, v.data());
+    // the arenas that exist, in file order: params; m, v once an AdamW or LAMB step has run; the EMA while it
+    // is on; the momentum buffer once a momentum step has run
+    const float* dev[SEC_COUNT] = {t.params, t.adam_m, t.adam_m ? t.adam_v : nullptr, t.ema_on ? t.ema : nullptr,
+                                   t.sgd_buf && t.sgd_steps ? t.sgd_buf : nullptr};
+    std::vector<float> host[SEC_COUNT];
+    const float* sec[SEC_COUNT] = {};
+    for (int k = 0; k < SEC_COUNT; k++) {
+        if (!dev[k]) continue;
+        host[k].resize((size_t)t.n_params);
+        t.device_to_canon(dev[k], host[k].data());
+        sec[k] = host[k].data();
     }
     if (vit::has_error()) return 1;
-    return vit_checkpoint_write(path, &t.cfg, p.data(), t.adam_m ? m.data() : nullptr,
-                                t.adam_m ? v.data() : nullptr, t.adam_t, &t.adam_hp);
+    Header hd;
+    hd.cfg = t.cfg;
+    hd.step = t.adam_t;
+    hd.adamw = t.adam_hp;
+    hd.ema_decay = t.ema_d;
+    hd.ema_updates = t.ema_updates;
+    hd.momentum_steps = t.sgd_steps;
+    hd.sgd = t.sgd_hp;
+    return vit::ckpt::write(path, hd, sec);
 }
 int vit_trainer_load_checkpoint(vit_trainer_t* h, const char* path) {
+    using namespace vit::ckpt;
     auto& t = h->t;
     if (!t.ema_unlocked("vit_trainer_load_checkpoint")) return 1;
-    vit_checkpoint_info_t info;
-    if (vit_checkpoint_read_info(path, &info)) return 1;
-    std::vector<float> p((size_t)t.n_params), m, v, e;
-    float e_decay = 0.f;
-    long long e_updates = 0;
-    int has_ema = 0;
-    if (vit_checkpoint_read_ema(path, &t.cfg, nullptr, &e_decay, &e_updates, &has_ema)) return 1;
-    if (has_ema) {
-        if (!(e_decay > 0.f && e_decay < 1.f)) {
-            set_error("checkpoint %s: EMA decay %g outside (0, 1)", path, (double)e_decay);
-            return 1;
-        }
-        e.resize((size_t)t.n_params);
-        if (vit_checkpoint_read_ema(path, &t.cfg, e.data(), nullptr, nullptr, nullptr)) return 1;
-    }
-    std::vector<float> b;
-    vit_sgd_t b_hp{0.f, 0.f, 0.f, 0};
-    long long b_steps = 0;
-    int has_mom = 0;
-    if (vit_checkpoint_read_momentum(path, &t.cfg, nullptr, &b_hp, &b_steps, &has_mom)) return 1;
-    if (has_mom) {
-        if (b_steps < 0 || !vit::Trainer::sgd_valid(b_hp.momentum, b_hp.dampening, b_hp.weight_decay, b_hp.nesterov)) {
-            set_error("checkpoint %s: invalid momentum-SGD setting in the header", path);
-            return 1;
-        }
-        b.resize((size_t)t.n_params);
-        if (vit_checkpoint_read_momentum(path, &t.cfg, b.data(), nullptr, nullptr, nullptr)) return 1;
-    }
-    if (info.has_opt) {
-        m.resize((size_t)t.n_params);
-        v.resize((size_t)t.n_params);
-    }
-    if (vit_checkpoint_read(path, &t.cfg, p.data(), info.has_opt ? m.data() : nullptr,
-                            info.has_opt ? v.data() : nullptr))
+    Reader r;
+    if (r.open(path) || r.require_config(&t.cfg)) return 1;
+    const Header& hd = r.header();
+    if (hd.has(SEC_EMA) && !(hd.ema_decay > 0.f && hd.ema_decay < 1.f)) {
+        set_error("checkpoint %s: EMA decay %g outside (0, 1)", path, (double)hd.ema_decay);
         return 1;
+    }
+    const vit_sgd_t& sg = hd.sgd;
+    if (hd.has(SEC_MOMENTUM) &&
+        (hd.momentum_steps < 0 || !vit::Trainer::sgd_valid(sg.momentum, sg.dampening, sg.weight_decay, sg.nesterov))) {
+        set_error("checkpoint %s: invalid momentum-SGD setting in the header", path);
+        return 1;
+    }
+    // every present section into host memory before the device is touched: a failing load changes nothing
+    std::vector<float> host[SEC_COUNT];
+    for (int k = 0; k < SEC_COUNT; k++) {
+        if (!hd.has((Section)k)) continue;
+        host[k].resize((size_t)t.n_params);
+        if (r.read((Section)k, host[k].data())) return 1;
+    }
     VIT_HIP(hipDeviceSynchronize());
-    t.canon_to_device(p.data(), t.params);
+    t.canon_to_device(host[SEC_PARAMS].data(), t.params);
     t.refresh_bf16();
-    if (info.has_opt) {
+    if (hd.has(SEC_M)) {
         if (!t.ensure_adam()) return 1;
-        t.canon_to_device(m.data(), t.adam_m);
-        t.canon_to_device(v.data(), t.adam_v);
-        t.adam_t = info.step;
-        t.adam_hp = info.adamw;
+        t.canon_to_device(host[SEC_M].data(), t.adam_m);
+        t.canon_to_device(host[SEC_V].data(), t.adam_v);
+        t.adam_t = hd.step;
+        t.adam_hp = hd.adamw;
     } else if (t.adam_m) {  // a parameters-only file restarts the optimizer
         VIT_HIP(hipMemsetAsync(t.adam_m, 0, t.arena_elems * 4, t.s));
         VIT_HIP(hipMemsetAsync(t.adam_v, 0, t.arena_elems * 4, t.s));
         t.adam_t = 0;
     }
-    if (has_mom) {  // the file's buffer, count and setting
+    if (hd.has(SEC_MOMENTUM)) {  // the file's buffer, count and setting
         if (!t.ensure_sgd_buf()) return 1;
-        t.canon_to_device(b.data(), t.sgd_buf);
-        t.sgd_steps = b_steps;
-        t.set_sgd(b_hp.momentum, b_hp.dampening, b_hp.weight_decay, b_hp.nesterov);
+        t.canon_to_device(host[SEC_MOMENTUM].data(), t.sgd_buf);
+        t.sgd_steps = hd.momentum_steps;
+        t.set_sgd(sg.momentum, sg.dampening, sg.weight_decay, sg.nesterov);
     } else {  // a file without one: the next momentum step seeds the buffer again; the setting stays
         t.sgd_steps = 0;
     }
-    if (has_ema) {  // the file's average, decay and count; EMA on
-        if (!t.ema && !(t.ema = t.alloc<float>(t.arena_elems))) return 1;
-        t.canon_to_device(e.data(), t.ema);
-        t.ema_set_decay(e_decay);
-        t.ema_updates = e_updates;
+    if (hd.has(SEC_EMA)) {  // the file's average, decay and count; EMA on
+        if (!t.ensure_arena(t.ema, false)) return 1;
+        t.canon_to_device(host[SEC_EMA].data(), t.ema);
+        t.ema_set_decay(hd.ema_decay);
+        t.ema_updates = hd.ema_updates;
         t.ema_on = true;
     } else if (t.ema_on) {  // a file without one restarts the average from the loaded parameters
         if (!t.ema_seed()) return 1;
