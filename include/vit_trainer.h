@@ -343,19 +343,9 @@ int vit_trainer_dp_ranks(vit_trainer_t* t);
 int vit_trainer_set_concurrency(vit_trainer_t* t, int on);
 /* ---- tuning options for A/B measurements in one process (call between steps):
  *      "microbatch" = number of micro-batch streams wanted (1 .. 4; the largest divisor of B),
- *      "dgrad_transposed" = 1 (default): dgrad GEMMs read the transposed weight copy,
- *      "fp8_ln_mx" = 1 (default): fp8 mode's LayerNorm forwards write the MX forms directly,
- *      "fp8_lnb_mx" = 1 (default): ... and its residual-gradient LayerNorm backwards those of dres,
- *      "head_splitk" = 1 (default): bf16 / fp8 modes split the classifier head's GEMMs at about
- *      four K-steps per work item (0: the fp32 engine's own split rule),
  *      "early_sgd" = -1 (default: on in fp8 mode, off in bf16; measured per dtype): one GPU, bf16 / fp8, concurrency on: vit_trainer_train_step
  *      updates each gradient chunk (head, layer L-1 .. 0, embedding) as soon as the backward has
  *      finished it, on a side stream beside the rest of the backward (same bits as one pass),
- *      "pre_side" = 1 (default): bf16 / fp8 modes with concurrency on clear the gradient arena
- *      (vit_trainer_zero_grad) and refresh the transposed weight copies on the weight-gradient
- *      stream beside the forward; the backward (and every host read) waits for them,
- *      "patch_tail" = 1 (default): bf16 / fp8 modes split the patch embedding's weight gradient for
- *      80 % of the GPU and run its small gradients on a second stream beside it (0: one stream, 45 %),
  *      "clip_overlap" = -1 (default: auto = 0 in bf16 and fp8 mode, measured): with
  *      gradient clipping on, bf16 / fp8 and concurrency on, 1 takes each gradient chunk's partial
  *      sums of squares on the side (all-reduce) stream as soon as the backward has finished the

@@ -262,6 +262,22 @@ def test_trainer_step_is_bitwise_deterministic(gpu, prec_name, nmb):
         assert np.array_equal(p0, p1)
 
 
+def test_retired_options_are_unknown(gpu):
+    """The options whose measured winner became the only path (remaining switches) fail like any
+    unknown name; an option that tests still use as a reference does not."""
+    v = gpu
+    cfg = v.data.CONFIGS["test_h64"]
+    m = v.ViT.build(cfg, 2, v.VIT_BF16, params=v.data.init_params(cfg, "parity", seed=23))
+    try:
+        for name in ("dgrad_transposed", "pre_side", "patch_tail", "head_splitk", "fp8_ln_mx", "fp8_lnb_mx",
+                     "fp8_ln_leftover"):
+            with pytest.raises(v.VitError, match="unknown option"):
+                m.set_option(name, 1)
+        m.set_option("microbatch", 2)
+    finally:
+        m.close()
+
+
 def test_vit_l16_full_size_step(gpu):
     """BASELINE config 4 shapes on one GPU (ViT-L/16, 224^2, C=1024, L=24, NH=16, B=256 per GPU,
     bf16): the same size-independent properties as the B/16 step.  The DP=8 exchange is the

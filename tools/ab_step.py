@@ -1,8 +1,8 @@
 """A/B of full training steps in ONE process (cdna_hip_programming.md §5.4 rule 24): configs are
 applied between steps and interleaved round by round; the median ms/step per config is printed.
     python tools/ab_step.py "gemm_debug=0|gemm_debug=4" [--rounds 4 --steps 3]
-A config is `key=value` pairs joined by `,`: trainer options (microbatch, dgrad_transposed),
-concurrency (0/1), gemm_variant, gemm_debug.  --dtype fp8 for the MXFP8 step (option fp8_ln_mx)."""
+A config is `key=value` pairs joined by `,`: trainer options (microbatch, last_cls, early_sgd),
+concurrency (0/1), gemm_variant, gemm_debug.  --dtype fp8 for the MXFP8 step."""
 import argparse
 import os
 import sys

@@ -22,7 +22,7 @@ def main():
     ap.add_argument("--colsum", action="store_true", help="backward with the fused qkv-bias gradient (trainer form)")
     ap.add_argument("--env-ab", default=None,
                     help="A/B of backward environments in one process, interleaved round by round, e.g. "
-                         "'VIT_ATTN_BWD_NOPAD=0|VIT_ATTN_BWD_NOPAD=1' (median of --rounds)")
+                         "'VIT_ATTN_BWD=persistent|VIT_ATTN_BWD=one' (median of --rounds)")
     ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     if args.generic:

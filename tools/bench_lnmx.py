@@ -52,7 +52,7 @@ def main():
         t_ln, t_rc, t_mx = timed(L, ln, a.iters), timed(L, rc, a.iters), timed(L, mx, a.iters)
         vit.check("lnmx")
         e = R * C
-        print(f"[{R} x {C}] VIT_LNMX_XMAP={os.environ.get('VIT_LNMX_XMAP', '1')}: ln_bf16 {t_ln:7.1f} us "
+        print(f"[{R} x {C}]: ln_bf16 {t_ln:7.1f} us "
               f"({6 * e / t_ln / 1e6:5.2f} TB/s)  rowcol {t_rc:7.1f} us ({4 * e / t_rc / 1e6:5.2f} TB/s)  "
               f"pair {t_ln + t_rc:7.1f} us  ln_mx {t_mx:7.1f} us ({6 * e / t_mx / 1e6:5.2f} TB/s)", flush=True)
 

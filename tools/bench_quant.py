@@ -41,7 +41,7 @@ def main():
             L.vit_sync()
             us = L.vit_event_elapsed_ms(e0, e1) * 1e3 / a.iters
             byts = R * C * 2 + R * C + R * C // 32 + (R * C + R * C // 32 if name == "rowcol" else 0)
-            print(f"{name} VIT_ROWCOL_COLS={os.environ.get('VIT_ROWCOL_COLS', 'auto')} [{R} x {C}]: {us:8.1f} us  "
+            print(f"{name} [{R} x {C}]: {us:8.1f} us  "
                   f"{byts / us / 1e6:6.2f} TB/s", flush=True)
             vit.check("quant")
 

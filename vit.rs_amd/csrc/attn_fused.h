@@ -253,9 +253,7 @@ constexpr int fwd_lds_bytes() { return NKT * 16 * (Geo<HS>::SK + Geo<HS>::SV) * 
 template <int HS, int NKT>
 constexpr int fwd_occ() { return fwd_lds_bytes<HS, NKT>() <= 80 * 1024 ? 2 : 1; }
 
-#ifndef VIT_ATTN_FWD_BUF
-#define VIT_ATTN_FWD_BUF 1  // K / V staging, Q loads and output / lse stores as buffer operations (no branches in the loop)
-#endif
+// K / V staging, Q loads and output / lse stores are buffer operations (no branches in the loop)
 // NS: key tiles that hold a key (< T) -- the score MFMAs, the mask and the exponentials skip the
 // all-padding tiles (NKT - NS of them, at most one: TP rounds T up to 32); P.V still runs NKT/2 pairs
 template <int HS, int NKT, int NS = NKT>
@@ -278,55 +276,41 @@ __global__ __launch_bounds__(256, (fwd_occ<HS, NKT>())) void attn_fwd_k(bf16_t* 
     // Branch-free Q loads and output stores (buffer operations: rows >= T read 0 / are dropped) let
     // hipcc count the loop's vmcnt: the next tile's Q loads are waited for, the previous tile's
     // stores stay in flight (with the "if (q < T)" stores and "row < T" loads it waited vmcnt(0))
-    [[maybe_unused]] const auto rq = buf_rsrc(base, (uint32_t)(T * C3 * 2));
-    [[maybe_unused]] const auto ro = buf_rsrc(out + (long long)b * T * C + h * HS, (uint32_t)(T * C * 2));
-    [[maybe_unused]] const auto rl = buf_rsrc(lse + (long long)bh * T, (uint32_t)(T * 4));
+    const auto rq = buf_rsrc(base, (uint32_t)(T * C3 * 2));
+    const auto ro = buf_rsrc(out + (long long)b * T * C + h * HS, (uint32_t)(T * C * 2));
+    const auto rl = buf_rsrc(lse + (long long)bh * T, (uint32_t)(T * 4));
     auto load_q = [&](int qt, bf16x8_t (&qf)[G::KS]) {
 #pragma unroll
-        for (int s = 0; s < G::KS; s++) {
-            if constexpr (VIT_ATTN_FWD_BUF) qf[s] = frag_buf<HS>(rq, (uint32_t)(C3 * 2), qt * 16 + i, s, lane);
-            else qf[s] = frag_glb<HS>(base, C3, qt * 16 + i, T, s, lane);
-        }
+        for (int s = 0; s < G::KS; s++) qf[s] = frag_buf<HS>(rq, (uint32_t)(C3 * 2), qt * 16 + i, s, lane);
     };
     const int nqt = (T + 15) / 16;
     bf16x8_t qn[G::KS];
     load_q(w, qn);
-    if constexpr (VIT_ATTN_FWD_BUF) {
-        // K | V rows through one resource from K's first column (every byte of rows >= T is past its
-        // end, so those rows read 0 without a branch); all loads before the first LDS store
-        const auto rkv = buf_rsrc(base + C, (uint32_t)(T * C3 * 2 - 2 * C));
-        constexpr int CH = G::CH, PER = (TP * CH + 255) / 256;
-        uint4 v[2][PER];
+    // K | V rows through one resource from K's first column (every byte of rows >= T is past its
+    // end, so those rows read 0 without a branch); all loads before the first LDS store
+    const auto rkv = buf_rsrc(base + C, (uint32_t)(T * C3 * 2 - 2 * C));
+    constexpr int CH = G::CH, PER = (TP * CH + 255) / 256;
+    uint4 v[2][PER];
 #pragma unroll
-        for (int o = 0; o < 2; o++)
+    for (int o = 0; o < 2; o++)
 #pragma unroll
-            for (int j = 0; j < PER; j++) {
-                const int idx = j * 256 + (int)threadIdx.x, t = idx / CH, cc = idx - t * CH;
-                v[o][j] = buf_ld16(rkv, (uint32_t)t * (uint32_t)(C3 * 2) + (uint32_t)(o * C * 2) + 16 * cc);
-            }
+        for (int j = 0; j < PER; j++) {
+            const int idx = j * 256 + (int)threadIdx.x, t = idx / CH, cc = idx - t * CH;
+            v[o][j] = buf_ld16(rkv, (uint32_t)t * (uint32_t)(C3 * 2) + (uint32_t)(o * C * 2) + 16 * cc);
+        }
 #pragma unroll
-        for (int o = 0; o < 2; o++)
+    for (int o = 0; o < 2; o++)
 #pragma unroll
-            for (int j = 0; j < PER; j++) {
-                const int idx = j * 256 + (int)threadIdx.x, t = idx / CH, cc = idx - t * CH;
-                if ((TP * CH) % 256 == 0 || idx < TP * CH)
-                    *reinterpret_cast<uint4*>((o ? Vs + t * G::SV : Ks + t * G::SK) + cc * 8) = v[o][j];
-            }
-    } else {
-        bf16_t* const img[2] = {Ks, Vs};
-        const int st[2] = {G::SK, G::SV};
-        const bf16_t* const src[2] = {base + C, base + 2 * C};
-        const long long ld[2] = {C3, C3};
-        load_images<HS, TP, 256, 2>(img, st, src, ld, T);
-    }
+        for (int j = 0; j < PER; j++) {
+            const int idx = j * 256 + (int)threadIdx.x, t = idx / CH, cc = idx - t * CH;
+            if ((TP * CH) % 256 == 0 || idx < TP * CH)
+                *reinterpret_cast<uint4*>((o ? Vs + t * G::SV : Ks + t * G::SK) + cc * 8) = v[o][j];
+        }
     ATTN_STAMP(1);
     __syncthreads();
     ATTN_STAMP(2);
     const float c = LOG2E / sqrtf((float)HS);
-#ifndef VIT_ATTN_FWD_SPLIT
-#define VIT_ATTN_FWD_SPLIT 1  // K row fragments as separate ds_read_b64 (RowBases); 0: hipcc merges them into ds_read2_b64
-#endif
-    const RowBases<HS> kb(Ks, G::SK, lane);
+    const RowBases<HS> kb(Ks, G::SK, lane);  // K row fragments as separate ds_read_b64 (hipcc merged plain reads into ds_read2_b64)
     for (int qt = w; qt < nqt; qt += 4) {
         const int q = qt * 16 + i;
         it = qt / 4;
@@ -342,10 +326,7 @@ __global__ __launch_bounds__(256, (fwd_occ<HS, NKT>())) void attn_fwd_k(bf16_t* 
         for (int kt = 0; kt < NS; kt++) {
             f32x4_t a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int s = 0; s < G::KS; s++) {
-                if constexpr (VIT_ATTN_FWD_SPLIT) a = mfma(kb.frag(kt * 16, G::SK, s), qf[s], a);
-                else a = mfma(frag_row<HS>(Ks, G::SK, kt * 16, s, lane), qf[s], a);
-            }
+            for (int s = 0; s < G::KS; s++) a = mfma(kb.frag(kt * 16, G::SK, s), qf[s], a);
             sacc[kt] = a;
         }
         ATTN_STAMP(1);
@@ -365,44 +346,25 @@ __global__ __launch_bounds__(256, (fwd_occ<HS, NKT>())) void attn_fwd_k(bf16_t* 
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         mx *= c;
-        float l = 0.f;
-#ifndef VIT_ATTN_FWD_PK
-#define VIT_ATTN_FWD_PK 1  // exponent arguments as packed fp32 (v_pk_fma_f32)
-#endif
-#ifndef VIT_ATTN_FWD_PAIRSUM
-#define VIT_ATTN_FWD_PAIRSUM 1  // two row-sum chains + v_rcp / v_log (r06; fp8 curve re-recorded)
-#endif
-        if constexpr (VIT_ATTN_FWD_PK) {
-            // r06: the row sum as two chains (even / odd score of each pair) and
-            // 1 / l, log2 l on v_rcp_f32 / v_log_f32.  Both change the rounding of l / lse within every
-            // oracle gate of the attention and model tests; the fp8 loss-curve fixture, a drift alarm,
-            // was re-recorded under the rule in tests/golden/make_fp8_curve.py.
-            typedef float f32x2_t __attribute__((ext_vector_type(2)));
-            const f32x2_t c2 = {c, c}, m2 = {-mx, -mx};
-            float l1 = 0.f;
+        // Exponent arguments as packed fp32 (v_pk_fma_f32); the row sum as two chains (even / odd score
+        // of each pair) and 1 / l, log2 l on v_rcp_f32 / v_log_f32.  Both change the rounding of l / lse
+        // within every oracle gate of the attention and model tests; the fp8 loss-curve fixture, a drift
+        // alarm, was re-recorded under the rule in tests/golden/make_fp8_curve.py.
+        typedef float f32x2_t __attribute__((ext_vector_type(2)));
+        const f32x2_t c2 = {c, c}, m2 = {-mx, -mx};
+        float l = 0.f, l1 = 0.f;
 #pragma unroll
-            for (int kt = 0; kt < NS; kt++)
+        for (int kt = 0; kt < NS; kt++)
 #pragma unroll
-                for (int r = 0; r < 4; r += 2) {
-                    const f32x2_t x = {sacc[kt][r], sacc[kt][r + 1]};
-                    const f32x2_t y = __builtin_elementwise_fma(x, c2, m2);
-                    sacc[kt][r] = fexp2(y.x);
-                    sacc[kt][r + 1] = fexp2(y.y);
-                    l += sacc[kt][r];
-                    if constexpr (VIT_ATTN_FWD_PAIRSUM) l1 += sacc[kt][r + 1];
-                    else l += sacc[kt][r + 1];
-                }
-            if constexpr (VIT_ATTN_FWD_PAIRSUM) l += l1;
-        } else {
-#pragma unroll
-            for (int kt = 0; kt < NS; kt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const float p = fexp2(fmaf(sacc[kt][r], c, -mx));
-                    sacc[kt][r] = p;
-                    l += p;
-                }
-        }
+            for (int r = 0; r < 4; r += 2) {
+                const f32x2_t x = {sacc[kt][r], sacc[kt][r + 1]};
+                const f32x2_t y = __builtin_elementwise_fma(x, c2, m2);
+                sacc[kt][r] = fexp2(y.x);
+                sacc[kt][r + 1] = fexp2(y.y);
+                l += sacc[kt][r];
+                l1 += sacc[kt][r + 1];
+            }
+        l += l1;
         l += __shfl_xor(l, 16, 64);
         l += __shfl_xor(l, 32, 64);
         ATTN_STAMP(2);
@@ -416,25 +378,16 @@ __global__ __launch_bounds__(256, (fwd_occ<HS, NKT>())) void attn_fwd_k(bf16_t* 
             for (int dt = 0; dt < G::DT; dt++) o[dt] = mfma(frag_tr(Vs, G::SV, 32 * ks, 16 * dt, lane), pb, o[dt]);
         }
         ATTN_STAMP(3);
-        if constexpr (VIT_ATTN_FWD_BUF) {
-            // every lane stores: rows q >= T fall past the resources' ends; the four lanes of a query
-            // write the same lse value
-            const float inv = VIT_ATTN_FWD_PAIRSUM ? __builtin_amdgcn_rcpf(l) : 1.0f / l;
-            const uint32_t off = (uint32_t)q * (uint32_t)(C * 2) + 8u * g;
+        // every lane stores: rows q >= T fall past the resources' ends; the four lanes of a query
+        // write the same lse value
+        const float inv = __builtin_amdgcn_rcpf(l);
+        const uint32_t off = (uint32_t)q * (uint32_t)(C * 2) + 8u * g;
 #pragma unroll
-            for (int dt = 0; dt < G::DT; dt++) {
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, pack4_bf16(o[dt], inv)), ro,
-                                                      off + 32u * dt, 0, 0);
-            }
-            __builtin_amdgcn_raw_buffer_store_b32(
-                __builtin_bit_cast(uint32_t, mx + (VIT_ATTN_FWD_PAIRSUM ? __builtin_amdgcn_logf(l) : log2f(l))), rl, 4u * q, 0, 0);
-        } else if (q < T) {
-            const float inv = 1.0f / l;
-            bf16_t* dst = out + ((long long)b * T + q) * C + h * HS + 4 * g;
-#pragma unroll
-            for (int dt = 0; dt < G::DT; dt++) store4(dst + 16 * dt, o[dt], inv);
-            if (g == 0) lse[(long long)bh * T + q] = mx + log2f(l);
+        for (int dt = 0; dt < G::DT; dt++) {
+            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, pack4_bf16(o[dt], inv)), ro,
+                                                  off + 32u * dt, 0, 0);
         }
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, mx + __builtin_amdgcn_logf(l)), rl, 4u * q, 0, 0);
         ATTN_STAMP(4);
     }
     it = 15;
@@ -815,20 +768,13 @@ __global__ __launch_bounds__(256, (bwd_occ<HS, NKT>())) void attn_bwd_pair_k(
 // attn_bwd1_k (one workgroup per item, blocking prologue) where the persistent LDS does not fit.
 constexpr int BWD_SDS = 48;          // dS^T [key][query] row stride: (SDS/2) = 8*odd dwords (tr reads)
 constexpr int ATTN_PART_ROWS = 16;   // column-sum partial rows per (b,h) a backward kernel may write
-// slice-image and dS^T row strides (elements): the swizzled images at head size 64 (sl_off, ds_off)
-// VIT_ATTN_SW_SLICE: swizzled 128-B slice rows (conflict-free transposed reads, more address
-// registers) vs the padded stride; the dS^T swizzle is always on at head size 64
-#ifndef VIT_ATTN_SW_SLICE
-#define VIT_ATTN_SW_SLICE 1
-#endif
-
+// slice-image and dS^T row strides (elements): the swizzled images at head size 64 (sl_off, ds_off);
+// swizzled 128-B slice rows give conflict-free transposed reads for more address registers than
+// the padded stride
 template <int HS>
-constexpr bool sw_slice() { return HS == 64 && VIT_ATTN_SW_SLICE; }
-#ifndef VIT_ATTN_SW_DS
-#define VIT_ATTN_SW_DS 1
-#endif
+constexpr bool sw_slice() { return HS == 64; }
 template <int HS>
-constexpr bool sw_ds() { return HS == 64 && VIT_ATTN_SW_DS; }
+constexpr bool sw_ds() { return HS == 64; }
 template <int HS>
 constexpr int slice_stride() { return sw_slice<HS>() ? 64 : Geo<HS>::SK; }
 template <int HS>
@@ -873,10 +819,8 @@ struct BwdRegs {  // per-wave state of the one-pass backward: the wave owns KK 1
 // slice's lse / delta, dSk = dS^T rows of the wave's first key
 // MASK: for operands whose rows past T are copies of row T-1 (not zero), the probabilities
 // of padded queries (q >= T) and keys (key >= T) are masked to 0 (nq / nk: valid queries / keys
-// counted from the slice's and the wave's first one)
-#ifndef VIT_ATTN_AHOIST
-#define VIT_ATTN_AHOIST 0  // phase A: all reads / score MFMAs first, 1-3: transposed reads all / half / none hoisted (0: per 16-query half; 1-3 spill at ViT-B/16)
-#endif
+// counted from the slice's and the wave's first one).  Works per 16-query half: hoisting all reads
+// and score MFMAs in front of the exponentials spilled at ViT-B/16.
 template <int HS, int KK = 2, bool MASK = false>
 __device__ __forceinline__ void bwd_slice_a(BwdRegs<HS, KK>& R, const bf16_t* Qc, const bf16_t* Dc, const float* lq_s,
                                             const float* dl_s, bf16_t* dSk, float c, int lane, int nq = 0,
@@ -896,78 +840,6 @@ __device__ __forceinline__ void bwd_slice_a(BwdRegs<HS, KK>& R, const bf16_t* Qc
             tq = frag_tr(Qc, SK, 0, 16 * dt, lane);
         }
     };
-#if VIT_ATTN_AHOIST
-    // Every LDS read first (both 16-query halves' row fragments, lse / delta), then all 16 score
-    // MFMAs, then the transposed fragments of the dV / dK products, requested before the
-    // exponentials so they land under them.  Same products and sums in the same order as the
-    // per-half form below (bit-identical); it waited on each half's reads and on the transposed
-    // reads right in front of the MFMAs that consume them.
-    bf16x8_t qr[2][KS], dr[2][KS];
-    float lq[2][4], dq[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-#pragma unroll
-        for (int s = 0; s < KS; s++) {
-            if constexpr (SW) {
-                qr[u][s] = frag_row_sw(reinterpret_cast<const char*>(Qc), 16 * u, s, lane);
-                dr[u][s] = frag_row_sw(reinterpret_cast<const char*>(Dc), 16 * u, s, lane);
-            } else {
-                qr[u][s] = frag_row<HS>(Qc, SK, 16 * u, s, lane);
-                dr[u][s] = frag_row<HS>(Dc, SK, 16 * u, s, lane);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            lq[u][r] = lq_s[16 * u + 4 * g + r];
-            dq[u][r] = dl_s[16 * u + 4 * g + r];
-        }
-    }
-    f32x4_t sa[KK][2], pa[KK][2];
-#pragma unroll
-    for (int u = 0; u < 2; u++)
-#pragma unroll
-        for (int kk = 0; kk < KK; kk++) {
-            f32x4_t s_ = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < KS; s++) {
-                s_ = mfma(qr[u][s], R.kf[kk][s], s_);
-                dp = mfma(dr[u][s], R.vf[kk][s], dp);
-            }
-            sa[kk][u] = s_;
-            pa[kk][u] = dp;
-        }
-    // VIT_ATTN_AHOIST 1: all DT transposed pairs before the exponentials; 2: the first TRH of them
-    constexpr int TRH = VIT_ATTN_AHOIST == 1 ? DT : VIT_ATTN_AHOIST == 2 ? (DT + 1) / 2 : 0;
-    bf16x8_t td[DT], tq[DT];
-#pragma unroll
-    for (int dt = 0; dt < TRH; dt++) tr_frags(dt, td[dt], tq[dt]);
-#pragma unroll
-    for (int u = 0; u < 2; u++)
-#pragma unroll
-        for (int kk = 0; kk < KK; kk++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float pv = fexp2(sa[kk][u][r] * c - lq[u][r]);
-                if constexpr (MASK) pv = (16 * u + 4 * g + r < nq && 16 * kk + i < nk) ? pv : 0.f;
-                P[kk][u][r] = pv;
-                dS[kk][u][r] = pv * (pa[kk][u][r] - dq[u][r]);
-                R.sds[kk] += dS[kk][u][r];
-            }
-#pragma unroll
-    for (int kk = 0; kk < KK; kk++) {
-        pb[kk] = pack_acc(P[kk][0], P[kk][1]);
-        db[kk] = pack_acc(dS[kk][0], dS[kk][1]);
-    }
-#pragma unroll
-    for (int dt = TRH; dt < DT; dt++) tr_frags(dt, td[dt], tq[dt]);
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++)
-#pragma unroll
-        for (int kk = 0; kk < KK; kk++) {
-            R.dv[kk][dt] = mfma(td[dt], pb[kk], R.dv[kk][dt]);
-            R.dk[kk][dt] = mfma(tq[dt], db[kk], R.dk[kk][dt]);
-        }
-#else
 #pragma unroll
     for (int u = 0; u < 2; u++) {
         bf16x8_t qr[KS], dr[KS];
@@ -1020,7 +892,6 @@ __device__ __forceinline__ void bwd_slice_a(BwdRegs<HS, KK>& R, const bf16_t* Qc
             R.dk[kk][dt] = mfma(tq, db[kk], R.dk[kk][dt]);
         }
     }
-#endif
     // dS^T -> LDS [key][query] (bf16, the MFMA operand's values): 4 consecutive queries per lane
     // and tile.  Without MASK, padded keys carry P != 0 (their K, V rows are zero): their dS is
     // finite and multiplies the zero K rows in dQ.  dSk = the wave's first key row.
@@ -1041,9 +912,6 @@ __device__ __forceinline__ void bwd_slice_a(BwdRegs<HS, KK>& R, const bf16_t* Qc
 // xk_ds / xk_k (XK): dS[q][T-1] per query of the slice and K[T-1] (fp32) of a key the kernel does not
 // own on the MFMA path (the XK side path): its rank-1 term dS[q][T-1] K[T-1] joins the dQ
 // accumulators before the store
-#ifndef VIT_ATTN_BLA
-#define VIT_ATTN_BLA 2  // phase B operand lookahead (blocks); 0: reads in front of each MFMA
-#endif
 template <int HS, int NSL, int NW, bool XK = false>
 __device__ __forceinline__ void bwd_slice_b(const bf16_t* Ks, const bf16_t* dSs, bf16_t* dq, long long C3, int q0,
                                             int T, float scale, int w, int lane, const float* xk_ds = nullptr,
@@ -1062,10 +930,9 @@ __device__ __forceinline__ void bwd_slice_b(const bf16_t* Ks, const bf16_t* dSs,
             if constexpr (SW) return frag_tr_ds(reinterpret_cast<const char*>(dSs), 32 * ks, 16 * u, lane);
             else return frag_tr(dSs, BWD_SDS, 32 * ks, 16 * u, lane);
         };
-#if VIT_ATTN_BLA
         // operands of block ks + BLA requested before block ks's MFMA (the unpipelined form waited for
         // each block's four reads right in front of its MFMA: an LDS round trip per MFMA)
-        constexpr int LA = VIT_ATTN_BLA < NSL ? VIT_ATTN_BLA : NSL;
+        constexpr int LA = 2 < NSL ? 2 : NSL;  // lookahead (blocks)
         bf16x8_t ra[LA], rb[LA];
 #pragma unroll
         for (int k = 0; k < LA; k++) {
@@ -1082,14 +949,6 @@ __device__ __forceinline__ void bwd_slice_b(const bf16_t* Ks, const bf16_t* dSs,
             if (ks & 1) acc1 = mfma(a, b, acc1);
             else acc = mfma(a, b, acc);
         }
-#else
-#pragma unroll
-        for (int ks = 0; ks < NSL; ks++) {
-            const bf16x8_t a = fa(ks), b = fb(ks);
-            if (ks & 1) acc1 = mfma(a, b, acc1);
-            else acc = mfma(a, b, acc);
-        }
-#endif
         acc += acc1;
         // lane (i,g): d = 16dt + 4g + r, q = q0 + 16u + i (padded queries: dS = 0)
         const int q = q0 + 16 * u + i;
@@ -1297,10 +1156,6 @@ __global__ __launch_bounds__(NKT / 2 * 64, 1) void attn_bwd1_k(bf16_t* __restric
         for (int s = 0; s < KS; s++) R.vf[kk][s] = frag_glb<HS>(base + 2 * C, C3, key0 + 16 * kk + i, T, s, lane);
     // one slice (32 rows) of Q and dO: PER 16-B pieces per thread and operand
     uint4 pq[PER], pd[PER];
-#ifndef VIT_ATTN_BWD1_BUF
-#define VIT_ATTN_BWD1_BUF 1
-#endif
-#if VIT_ATTN_BWD1_BUF
     // buffer loads (rows >= T read 0, no "zero, then load if in range" merge), lanes past the last
     // piece repeating one (put_slice skips them), and only the waves that own a piece
     const auto rq_s = buf_rsrc(base, (uint32_t)(T * C3 * 2)), rd_s = buf_rsrc(dbase, (uint32_t)(T * C * 2));
@@ -1315,19 +1170,6 @@ __global__ __launch_bounds__(NKT / 2 * 64, 1) void attn_bwd1_k(bf16_t* __restric
             pd[j] = buf_ld16(rd_s, r * (uint32_t)(C * 2) + 16 * c);
         }
     };
-#else
-    auto fetch_slice = [&](int q0) {
-#pragma unroll
-        for (int j = 0; j < PER; j++) {
-            const int idx = j * NT + tid, t = idx / CH, c = idx - t * CH;
-            pq[j] = pd[j] = make_uint4(0, 0, 0, 0);
-            if (idx < 32 * CH && q0 + t < T) {
-                pq[j] = *reinterpret_cast<const uint4*>(base + (long long)(q0 + t) * C3 + c * 8);
-                pd[j] = *reinterpret_cast<const uint4*>(dbase + (long long)(q0 + t) * C + c * 8);
-            }
-        }
-    };
-#endif
     auto put_slice = [&](int buf) {
 #pragma unroll
         for (int j = 0; j < PER; j++) {
@@ -1343,10 +1185,7 @@ __global__ __launch_bounds__(NKT / 2 * 64, 1) void attn_bwd1_k(bf16_t* __restric
     // query per thread their rows are requested here, before the K image's, so the prologue is one
     // memory round trip, not two (rows past T are clamped to row T-1 and their results dropped: no
     // branch around the loads)
-#ifndef VIT_ATTN_BWD1_EARLY
-#define VIT_ATTN_BWD1_EARLY 1
-#endif
-    constexpr bool EARLY = VIT_ATTN_BWD1_EARLY && TPQ <= NT;
+    constexpr bool EARLY = TPQ <= NT;
     uint4 ov[EARLY ? CH : 1], dv[EARLY ? CH : 1];
     float ls_e = INFINITY;
     if constexpr (EARLY) {
@@ -1466,14 +1305,11 @@ __global__ __launch_bounds__(NKT / 2 * 64, 1) void attn_bwd1_k(bf16_t* __restric
             }
         }
         if (sl + 1 < NSLQ) put_slice(cur ^ 1);  // its buffer was last read in the previous slice
-#ifndef VIT_ATTN_BWD1_VMWAIT
-#define VIT_ATTN_BWD1_VMWAIT 1
-#endif
         // every wave, every slice: the fetch's loads are complete here (put_slice waited for them on the
         // owning waves; the others issued none).  Without a wait hipcc sees on every path, it kept
         // the loads possibly pending on the non-owner path and waited vmcnt(0) before the next
         // fetch — after phase B's dQ stores, so every slice waited for its own stores to complete
-        if constexpr (VIT_ATTN_BWD1_VMWAIT) __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
         ATTN_STAMP(3);
         bwd_slice_b<HS, NSL, NW, XK>(Ks, dSs, dq, C3, q0, T, scale, w, lane, xds_s, xk_s);
         ATTN_STAMP(4);
@@ -1501,14 +1337,10 @@ __global__ __launch_bounds__(NKT / 2 * 64, 1) void attn_bwd1_k(bf16_t* __restric
     }
 }
 
-template <int HS, int NKT, int KK = 2>
-// VIT_ATTN_SKEW: the persistent backward runs phase B of slice s-1 right after phase A of slice s
-// (dS^T double-buffered), one barrier per slice instead of two, so the two phases' MFMA, VALU and
+// The persistent backward runs phase B of slice s-1 right after phase A of slice s (dS^T
+// double-buffered), one barrier per slice instead of two, so the two phases' MFMA, VALU and
 // LDS work share one barrier interval
-#ifndef VIT_ATTN_SKEW
-#define VIT_ATTN_SKEW 1
-#endif
-
+template <int HS, int NKT, int KK = 2>
 struct Bwdp {
     using G = Geo<HS>;
     static constexpr int TP = NKT * 16, NW = NKT / KK, NT = NW * 64, NSL = TP / 32, CH = G::CH;
@@ -1517,7 +1349,7 @@ struct Bwdp {
     static constexpr int V_OFF = K_OFF + 2 * TP * SV * 2;    // next item's V rows [TP][SK]
     static constexpr int Q_OFF = V_OFF + TP * SK * 2;        // Q slices [2][32][SL]
     static constexpr int D_OFF = Q_OFF + 2 * 32 * SL * 2;    // dO slices [2][32][SL]
-    static constexpr int NDS = VIT_ATTN_SKEW ? 2 : 1;       // dS^T buffers
+    static constexpr int NDS = 2;                            // dS^T buffers
     static constexpr int S_OFF = D_OFF + 2 * 32 * SL * 2;    // dS^T [NDS][TP][SDS]
     static constexpr int L_OFF = S_OFF + NDS * TP * SDS * 2; // lse [2][TP] (item parity)
     static constexpr int E_OFF = L_OFF + 2 * TP * 4;         // delta [2][32] (slice parity)
@@ -1541,18 +1373,11 @@ __global__ __launch_bounds__(NKT / KK * 64, 1) void attn_bwdp_k(bf16_t* __restri
                                                                const bf16_t* __restrict__ qkv,
                                                                const bf16_t* __restrict__ out,
                                                                const float* __restrict__ lse, int T,
-                                                               int C, int NH, int BH, float* __restrict__ dsum,
-                                                               int stagger) {
+                                                               int C, int NH, int BH, float* __restrict__ dsum) {
     using G = Geo<HS>;
     using Z = Bwdp<HS, NKT, KK>;
-    // stagger (100 MHz ticks, VIT_ATTN_STAGGER): every other CU of each XCD starts that much later, so
-    // the CUs' items do not all end (dK / dV store burst) at the same moment.  Measured (VERDICT r05
-    // item 3, B/16, two rounds): 0: 239.5 / 245.0 us, 400: 245.8 / 240.6, 870 (half an item): 248.0 /
-    // 248.0, 1300: 253.3 / 247.3 -- no gain (profiles/r06_attn_bwd_stagger.txt), so 0
-    if (stagger > 0 && ((blockIdx.x >> 3) & 1)) {
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        while (__builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)stagger) __builtin_amdgcn_s_sleep(8);
-    }
+    // (starting every other CU of each XCD later, so the items' dK / dV store bursts do not coincide,
+    // measured no gain at ViT-B/16: profiles/r06_attn_bwd_stagger.txt)
     constexpr int TP = Z::TP, NW = Z::NW, NT = Z::NT, NSL = Z::NSL, SK = Z::SK, SV = Z::SV, SL = Z::SL;
     static_assert((32 * G::CH) % 64 == 0 && NT % 64 == 0, "slice pieces are whole waves");
     constexpr int KS = G::KS, CH = G::CH, PER = Z::PER, PERS = Z::PERS;
@@ -1569,11 +1394,8 @@ __global__ __launch_bounds__(NKT / KK * 64, 1) void attn_bwdp_k(bf16_t* __restri
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int key0 = w * 16 * KK;
     // the waves that own a slice piece (PER = 1: the first 32 CH / 64); the others would fetch and
-    // store duplicates (VIT_ATTN_SLICE_ALL=1: every wave does, the pre-r05 form)
-#ifndef VIT_ATTN_SLICE_ALL
-#define VIT_ATTN_SLICE_ALL 0
-#endif
-    constexpr bool SPLIT_SLICE = !VIT_ATTN_SLICE_ALL && Bwdp<HS, NKT, KK>::PER == 1 && (32 * G::CH) % 64 == 0;
+    // store duplicates
+    constexpr bool SPLIT_SLICE = Bwdp<HS, NKT, KK>::PER == 1 && (32 * G::CH) % 64 == 0;
     const bool slice_wave = !SPLIT_SLICE || w < 32 * G::CH / 64;
     const float scale = 1.0f / sqrtf((float)HS);
     const float c = LOG2E * scale;
@@ -1696,44 +1518,30 @@ __global__ __launch_bounds__(NKT / KK * 64, 1) void attn_bwdp_k(bf16_t* __restri
                 // unconditional load (past T: 0); padded keys get +inf when it is put
                 if (sl == 0) lse_n = buf_ldf(s_nxt.l, 4 * tid);
             }
-            if constexpr (VIT_ATTN_SKEW) {
-                // A(sl) -> dS^T buffer sl&1; B(sl-1) from buffer (sl-1)&1 (complete since the last
-                // barrier); the slice buffers cur^1 were last read by A(sl-1), before that barrier
-                bf16_t* dS_a = dSs + (sl & 1) * TP * Z::SDS;
-                bwd_slice_a<HS, KK>(R, Qs + cur * 32 * SL, Ds + cur * 32 * SL, lse_cur + q0, del_s + cur * 32,
-                                    dS_a + key0 * Z::SDS, c, lane);
-                ATTN_STAMP(1);
-                if (sl > 0)
-                    bwd_slice_b<HS, NSL, NW>(Kimg + kb * TP * SV, dSs + ((sl - 1) & 1) * TP * Z::SDS, dq, C3,
-                                             q0 - 32, T, scale, w, lane);
-                ATTN_STAMP(2);
-                if (slice_wave) put_slice(cur ^ 1);
-                if (sl == 0 && tid < TP) lse_s[((n + 1) & 1) * TP + tid] = tid < T ? lse_n : INFINITY;
-                ATTN_STAMP(3);
-                __syncthreads();
-                ATTN_STAMP(4);
-                // the next item's K image / V rows: after the barrier, so every wave has finished
-                // this item's load_kv reads of the V rows (item start) before any block is replaced
-                put_side(kb ^ 1, sl);
-                ATTN_STAMP(5);
-            } else {
-                bwd_slice_a<HS, KK>(R, Qs + cur * 32 * SL, Ds + cur * 32 * SL, lse_cur + q0, del_s + cur * 32,
-                                    dSs + key0 * Z::SDS, c, lane);
-                __syncthreads();
-                // buffers written here were last read before the barrier above (slice buffer cur^1 by
-                // the previous slice, the idle K image by the previous item, the V rows by load_kv)
-                put_slice(cur ^ 1);
-                put_side(kb ^ 1, sl);
-                if (sl == 0 && tid < TP) lse_s[((n + 1) & 1) * TP + tid] = tid < T ? lse_n : INFINITY;
-                bwd_slice_b<HS, NSL, NW>(Kimg + kb * TP * SV, dSs, dq, C3, q0, T, scale, w, lane);
-                __syncthreads();
-            }
-        }
-        if constexpr (VIT_ATTN_SKEW) {  // the item's last phase B; the barrier also publishes the last put_side
-            bwd_slice_b<HS, NSL, NW>(Kimg + kb * TP * SV, dSs + ((NSL - 1) & 1) * TP * Z::SDS, dq, C3,
-                                     (NSL - 1) * 32, T, scale, w, lane);
+            // A(sl) -> dS^T buffer sl&1; B(sl-1) from buffer (sl-1)&1 (complete since the last
+            // barrier); the slice buffers cur^1 were last read by A(sl-1), before that barrier
+            bf16_t* dS_a = dSs + (sl & 1) * TP * Z::SDS;
+            bwd_slice_a<HS, KK>(R, Qs + cur * 32 * SL, Ds + cur * 32 * SL, lse_cur + q0, del_s + cur * 32,
+                                dS_a + key0 * Z::SDS, c, lane);
+            ATTN_STAMP(1);
+            if (sl > 0)
+                bwd_slice_b<HS, NSL, NW>(Kimg + kb * TP * SV, dSs + ((sl - 1) & 1) * TP * Z::SDS, dq, C3,
+                                         q0 - 32, T, scale, w, lane);
+            ATTN_STAMP(2);
+            if (slice_wave) put_slice(cur ^ 1);
+            if (sl == 0 && tid < TP) lse_s[((n + 1) & 1) * TP + tid] = tid < T ? lse_n : INFINITY;
+            ATTN_STAMP(3);
             __syncthreads();
+            ATTN_STAMP(4);
+            // the next item's K image / V rows: after the barrier, so every wave has finished
+            // this item's load_kv reads of the V rows (item start) before any block is replaced
+            put_side(kb ^ 1, sl);
+            ATTN_STAMP(5);
         }
+        // the item's last phase B; the barrier also publishes the last put_side
+        bwd_slice_b<HS, NSL, NW>(Kimg + kb * TP * SV, dSs + ((NSL - 1) & 1) * TP * Z::SDS, dq, C3,
+                                 (NSL - 1) * 32, T, scale, w, lane);
+        __syncthreads();
         ATTN_STAMP(6);
         bwd_item_end<HS, KK>(R, dq, C, key0, T, scale,
                              dsum ? dsum + ((long long)((bh / NH) * NW + w) * NH + bh % NH) * 3 * HS : nullptr, lane,
@@ -1760,10 +1568,7 @@ constexpr int max_tp() {
 template <int HS, int NKT>
 bool launch_fwd(bf16_t* out, float* lse, const bf16_t* qkv, int B, int T, int C, int NH, hipStream_t s) {
     if (T > NKT * 16 || T <= (NKT - 2) * 16) return false;  // the kernel masks keys in its last score tile only
-#ifndef VIT_ATTN_FWD_TRIM
-#define VIT_ATTN_FWD_TRIM 1
-#endif
-    if (VIT_ATTN_FWD_TRIM && (NKT - 1) * 16 >= T)
+    if ((NKT - 1) * 16 >= T)
         attn_fwd_k<HS, NKT, NKT - 1><<<B * NH, 256, 0, s>>>(out, lse, qkv, T, C, NH);
     else
         attn_fwd_k<HS, NKT><<<B * NH, 256, 0, s>>>(out, lse, qkv, T, C, NH);
@@ -1784,19 +1589,15 @@ int launch_bwd(bf16_t* dqkv, const bf16_t* dout, const bf16_t* qkv, const bf16_t
     if constexpr (bwdp_fits<HS, NK4, 4>()) {
         if (v == 4) {
             attn_bwdp_k<HS, NK4, 4><<<std::min(BH, attn_cu_count()), NK4 / 4 * 64, 0, s>>>(dqkv, dout, qkv, out, lse,
-                                                                                          T, C, NH, BH, part, 0);
+                                                                                          T, C, NH, BH, part);
             count_hit(VIT_HIT_ATTN_BWD_PERSISTENT);
             return NK4 / 4;
         }
     }
     if constexpr (bwdp_fits<HS, NKT, 2>()) {
         if (v == 0) {
-            static const int stagger = [] {
-                const char* e = getenv("VIT_ATTN_STAGGER");
-                return e ? atoi(e) : 0;
-            }();
             attn_bwdp_k<HS, NKT, 2><<<std::min(BH, attn_cu_count()), NKT / 2 * 64, 0, s>>>(dqkv, dout, qkv, out, lse,
-                                                                                         T, C, NH, BH, part, stagger);
+                                                                                         T, C, NH, BH, part);
             count_hit(VIT_HIT_ATTN_BWD_PERSISTENT);
             return NKT / 2;
         }

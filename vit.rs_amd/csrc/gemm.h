@@ -148,7 +148,6 @@ void gemm_set_variant(int v);
 void gemm_set_debug(int flags);
 // compute units of the current device: the persistent engines' grid (one workgroup per CU)
 int gemm_cu_count();
-int gemm_persist_grid();  // workgroups of the persistent engines (VIT_PERSIST_CUS; default gemm_cu_count())
 struct GemmParams;
 void gemm_set_trace(unsigned long long* trace);
 // variant 11: the two-group ping-pong engine (gemm_pp.hip, 192x256 tiles) for the shapes it takes

@@ -16,13 +16,6 @@
 
 #include <cstdlib>
 
-// one phase per K-step in the persistent engine (the fp8 engine's r06 form): measured slower for bf16
-// (per ViT-B/16 layer 2.595 / 2.601 vs 2.544 / 2.545 ms, step 36.13 / 36.02 vs 35.88 / 35.80 ms,
-// two interleaved rounds, profiles/r06_onephase.txt), so off
-#ifndef VIT_G2_ONEPHASE
-#define VIT_G2_ONEPHASE 0
-#endif
-
 namespace vit {
 
 // ============================================================================ bf16 MFMA GEMM
@@ -591,31 +584,12 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(GemmParams p) {
         for (int kt = 0; kt < nk; kt++) {
             const char* img = smem + sl * SLOT_BYTES;
             const int sl2 = (sl + 2) & 3;
-            // ---- phase 0
+            // ---- phase 0 (two phases per K-step: one phase, the fp8 engine's form, measured slower
+            // for bf16, step 36.13 / 36.02 vs 35.88 / 35.80 ms, profiles/r06_onephase.txt)
 #pragma unroll
             for (int b = 0; b < 4; b++) fb[b] = frag<true>(img + IMG_BYTES, wn * 64 + b * 16, lane);
 #pragma unroll
             for (int a = 0; a < 4; a++) alo[a] = frag<true>(img, wm * 128 + a * 16, lane);
-#if VIT_G2_ONEPHASE
-            // one phase per step: all 12 fragments read before one barrier, the 32 MFMAs after it
-            // (two barriers per step instead of four)
-#pragma unroll
-            for (int a = 0; a < 4; a++) ahi[a] = frag<true>(img, wm * 128 + (4 + a) * 16, lane);
-            issue_a(kt + 2, sl2, more);
-            issue_b(kt + 2, sl2, more);
-            // own pieces of the next step landed (the one after, 4 pieces, in flight); in a later
-            // tile's first step they were retired before the previous epilogue
-            if (kt > 0 || j == 0) {
-                if (kt + 2 < nk || more) wait_vm(4);
-                else wait_vm(0);
-            }
-            bar();
-            mfma_half(0, alo, fb);
-            mfma_half(1, ahi, fb);
-            bar();
-            sl = (sl + 1) & 3;
-            continue;
-#endif
             issue_a(kt + 2, sl2, more);
             bar();
             mfma_half(0, alo, fb);
@@ -643,11 +617,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(GemmParams p) {
         // last two slots done before they become staging space.  Through the builtin, not asm: hipcc
         // then knows no LDS-DMA is pending after the epilogue and does not put a vmcnt(0) in front
         // of the next tile's first fragment reads (it did: a wait for all of this epilogue's stores)
-#if VIT_G2_EPI_WAIT_ASM
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
         __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) expcnt(7) lgkmcnt(0), visible to the compiler (below)
-#endif
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1133,15 +1103,6 @@ int gemm_cu_count() {
     }();
     return n;
 }
-// workgroups of the persistent GEMM engines (VIT_PERSIST_CUS, A/B): default one per CU
-int gemm_persist_grid() {
-    static const int n = [] {
-        const char* e = getenv("VIT_PERSIST_CUS");
-        const int v = e ? atoi(e) : 0;
-        return v >= 64 && v <= gemm_cu_count() ? v : gemm_cu_count();
-    }();
-    return n;
-}
 bool gemm_streaming() { return gemm_variant() == 7 || gemm_variant() == 11; }
 void gemm_set_debug(int flags) { g_debug_flags = flags; }
 static int g_debug_flags_fwd() { return g_debug_flags; }
@@ -1159,13 +1120,9 @@ GemmParams make_gemm_params(const GemmArgs& a, int kchunk) {
     // persistent-engine tile order (bench_gemm, ViT-B/16 shapes, GM 0 / 4 / 8 / 16): groups of 8 row
     // panels help where the A panels are small (K <= 768: qkv fwd 188 -> 179 us, proj fwd 137 -> 133)
     // and hurt where they are large (K = 3072: fcproj fwd 289 -> 302, fc dgrad 235 -> 247: each A panel
-    // is then re-read once per column group); VIT_GEMM_GM overrides
-    static const int gm_env = [] {
-        const char* e = getenv("VIT_GEMM_GM");
-        return e && *e ? atoi(e) : -1;
-    }();
+    // is then re-read once per column group)
     const int gm_dbg = (g_debug_flags >> 16) & 0xF;  // diagnostic: (gm + 1) << 16 forces gm (tests)
-    p.gm = gm_dbg ? gm_dbg - 1 : gm_env >= 0 ? gm_env : (a.K <= 768 ? 8 : 0);
+    p.gm = gm_dbg ? gm_dbg - 1 : (a.K <= 768 ? 8 : 0);
     p.stagger = ((g_debug_flags >> 8) & 0xFF) * 50;  // debug: 0.5 us units
     p.trace = g_trace;
     p.mx_q = a.mx_q;
@@ -1301,7 +1258,7 @@ static void launch_g2(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStre
         if ((gemm_variant() == 7 || gemm_variant() == 11) && grid.y == 1 && p.K >= 2 * g2::BK &&
             (long long)p.M * p.lda * 2 < (1LL << 31) &&
             (long long)p.N * p.ldb * 2 < (1LL << 31)) {
-            const int cus = gemm_persist_grid();
+            const int cus = gemm_cu_count();
             const dim3 pg((int)grid.x < cus ? grid.x : cus);
             switch (a.epi) {
 #define VIT_CASE(E) \
@@ -1350,36 +1307,19 @@ static void launch_g2(const GemmArgs& a, const GemmParams& p, dim3 grid, hipStre
 }
 
 // split-K for two-workgroups-per-CU kernels, keeping >= 32 K-steps per split: the one-round rule
-// below (fill_pct > 0: the caller's fill target, else VIT_G4_FILL), falling back to the best fill
+// below (fill_pct > 0: the caller's fill target, else 45 %), falling back to the best fill
 // over any number of rounds of the 512 workgroup slots
 static int choose_split_g4(int tiles, int nk, int fill_pct = 0) {
-    // slots the split-K work items are sized for (VIT_G4_SLOTS, A/B): 512 = both workgroups of every CU
-    static const int slots = [] {
-        const char* e = getenv("VIT_G4_SLOTS");
-        const int v = e ? atoi(e) : 512;
-        return v >= 64 && v <= 2048 ? v : 512;
-    }();
-    // r06 rule: the smallest split whose work items fill >= `fill` of the slots in ONE round.  The weight
+    constexpr int slots = 512;  // the split-K work items are sized for both workgroups of every CU
+    // The smallest split whose work items fill >= `fill` of the slots in ONE round.  The weight
     // gradients run on their own stream beside the micro-batch streams, so a partly idle round costs
     // less than the slab bytes (and the fixed-order reduce) of more splits: ViT-B/16 splits 9/26/7/7 ->
-    // 8/23/6/6 (qkv/proj/fc/fcproj), ViT-H/14 qkv 10 -> 3 (profiles/r06_g4_slots.txt).  VIT_G4_RULE=0:
-    // the round-5 rule below alone (best fill, multi-round allowed, first >= 90 %)
-    static const bool one_round = [] {
-        const char* e = getenv("VIT_G4_RULE");
-        return !(e && e[0] == '0');
-    }();
-    // fill target 45 % (VIT_G4_FILL), as the fp8 engine's: 80 -> 45 % ViT-B/16 +0.2 / +0.4 %, ViT-H/14 bf16
+    // 8/23/6/6 (qkv/proj/fc/fcproj), ViT-H/14 qkv 10 -> 3 (profiles/r06_g4_slots.txt).
+    // Fill target 45 %, as the fp8 engine's: 80 -> 45 % ViT-B/16 +0.2 / +0.4 %, ViT-H/14 bf16
     // +2.2 %, ViT-L/16 -0.6 % (interleaved bench rounds, profiles/r06_g4_slots.txt)
-    static const double fill = [] {
-        const char* e = getenv("VIT_G4_FILL");
-        const int v = e ? atoi(e) : 45;
-        return (v >= 20 && v <= 100 ? v : 45) / 100.0;
-    }();
-    if (one_round) {
-        const double f = fill_pct > 0 ? fill_pct / 100.0 : fill;
-        const int s1 = (int)((f * slots + tiles - 1) / tiles);
-        if (s1 >= 1 && (long long)tiles * s1 <= slots && nk / s1 >= 32) return s1;
-    }
+    const double f = (fill_pct > 0 ? fill_pct : 45) / 100.0;
+    const int s1 = (int)((f * slots + tiles - 1) / tiles);
+    if (s1 >= 1 && (long long)tiles * s1 <= slots && nk / s1 >= 32) return s1;
     int best = 1;
     double best_eff = 0.0;
     for (int s = 1; s <= 64 && nk / s >= 32; s++) {

@@ -29,7 +29,7 @@ struct GemmParams {
     int colsum_row_period;
     int k_period;  // 256x128 engine: > 0 = walk only the K-steps holding a row i * k_period (GemmArgs::k_period)
     int gm;      // persistent engine tile order: groups of gm row panels, column-major inside a group
-                 // (0: row-major; VIT_GEMM_GM)
+                 // (0: row-major)
     uint8_t* mx_q;  // fused MX output (GemmArgs::mx_q / mx_s); mx_rg = padded rows / 32
     uint8_t* mx_s;
     int mx_rg;

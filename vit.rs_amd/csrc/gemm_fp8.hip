@@ -23,7 +23,6 @@
 // tile's scales are 512 contiguous bytes per operand, staged by one 4-byte LDS-DMA per wave;
 // each MFMA reads its lane's byte with one ds_read_u8.  Padding rows carry scale 0 (2^-127).
 #include <algorithm>
-#include <cstdlib>
 
 #include "gemm_common.h"
 #include "ln_common.h"
@@ -31,13 +30,6 @@
 
 #ifndef VIT_F8_TRACE
 #define VIT_F8_TRACE 0
-#endif
-// one phase per K-step in the streaming engine (two barriers per step instead of four): faster alone
-// (ViT-H/14 micro-batch GEMMs, tools/f8_trace.py: qkv fwd 146 -> 128 us, fc dgrad 187 -> 170, qkv dgrad
-// 152 -> 137) but slower in the sustained train step (117.0 vs 115.7 ms/step, two interleaved rounds;
-// profiles/r06_onephase.txt), so off
-#ifndef VIT_F8_ONEPHASE
-#define VIT_F8_ONEPHASE 0
 #endif
 
 namespace vit {
@@ -413,29 +405,8 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(F8Params fp) {
                 fa0[a] = frag(img, wm * 128 + a * 32, lane);
                 sa0[a] = scale_of(sc, wm * 4 + a, lane);
             }
-#if VIT_F8_ONEPHASE
-            // one phase per step: every fragment of the step read before one barrier, the 8 MFMAs
-            // after it (two barriers per step instead of four; 48 fragment VGPRs live at once)
-#pragma unroll
-            for (int a = 0; a < 2; a++) {
-                fa1[a] = frag(img, wm * 128 + (2 + a) * 32, lane);
-                sa1[a] = scale_of(sc, wm * 4 + 2 + a, lane);
-            }
-            issue_a(kt + 2, sl2, more);
-            issue_b(kt + 2, sl2, more);
-            // own pieces of the next step landed (the one after, 5 pieces, in flight); in a later
-            // tile's first step they were retired before the previous epilogue
-            if (kt > 0 || j == 0) {
-                if (kt + 2 < nk || more) wait_vm_t(5);
-                else wait_vm_t(0);
-            }
-            bar();
-            mfma_half(0, fa0, sa0, fb, sb_);
-            mfma_half(1, fa1, sa1, fb, sb_);
-            bar();
-            sl = (sl + 1) & 3;
-            continue;
-#endif
+            // two phases per K-step: one phase (two barriers instead of four) was faster alone but slower
+            // in the sustained train step (117.0 vs 115.7 ms/step, profiles/r06_onephase.txt)
             issue_a(kt + 2, sl2, more);
             bar();
             mfma_half(0, fa0, sa0, fb, sb_);
@@ -462,11 +433,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_s(F8Params fp) {
         float bpre[8];
         staged_bias_prefetch<EPI>(p, lane, cur.tn0 + wn * 64, bpre);
         // through the builtin so hipcc knows no LDS-DMA is pending afterwards (as g2::gemm_kernel_s)
-#if VIT_F8_EPI_WAIT_ASM
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
         __builtin_amdgcn_s_waitcnt(0x0070);
-#endif
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -731,21 +698,20 @@ __global__ __launch_bounds__(TOK * 2 * (COLS / 64)) void quantize_mx_rowcol_k(ui
 // ln_forward_bf16 + quantize_mx_rowcol_bf16 byte for byte.  Rows R .. Rpad-1 write zero row-form
 // scales; tokens R .. ntok-1 of the column form are zero padding (as quantize_mx_rowcol_k).
 // (two rows of loads in flight per wave: <= 128 VGPRs up to C = 1280, where two 80-KiB workgroups share a CU)
-// WB: the lane's LN weight / bias float4s held in registers for the wave's 4 rows (else re-read per row)
-// RPW: rows per wave (4: 8 waves, 512 threads, the default; 2: 16 waves, 1024 threads, every row's loads
-// issued at once: VIT_LNMX_RPW=2, measured 39.1 vs 36.4 us at 16448 x 1280, tools/bench_lnmx.py).
+// The lane's LN weight / bias float4s are held in registers for the wave's 4 rows.  Two rows per wave
+// (16 waves, every row's loads issued at once) measured 39.1 vs 36.4 us at 16448 x 1280 (tools/bench_lnmx.py).
 // Standalone it is at par with the pair it replaces (36.4 vs 37.5 us per ViT-H/14 micro-batch; 64.6 vs
 // 67.7 us for B = 128): a 32-token tile holds 80 KiB of LDS, so two workgroups per CU and 514 tiles
 // for 512 slots; in the train step the other micro-batch stream fills the gaps.
-template <int NV, bool WB, int RPW>
-__global__ __launch_bounds__(64 * 32 / RPW, (RPW == 2 || NV <= 5 ? 4 : 2)) void ln_fwd_mx_k(uint8_t* __restrict__ qr, uint8_t* __restrict__ slr,
+template <int NV>
+__global__ __launch_bounds__(512, (NV <= 5 ? 4 : 2)) void ln_fwd_mx_k(uint8_t* __restrict__ qr, uint8_t* __restrict__ slr,
                                                    uint8_t* __restrict__ qc, uint8_t* __restrict__ slc,
                                                    float* __restrict__ mean, float* __restrict__ rstd,
                                                    const float* __restrict__ x, const float* __restrict__ w,
                                                    const float* __restrict__ b, int R, int rgr_tot, long long ldqc,
-                                                   int tok_off, int ntok, int rgc_tot, int xmap, int nmain,
+                                                   int tok_off, int ntok, int rgc_tot, int nmain,
                                                    int ntiles, uint16_t* __restrict__ ybf) {
-    constexpr int C = 256 * NV, TOK = 32, NT = 64 * TOK / RPW;
+    constexpr int C = 256 * NV, TOK = 32, RPW = 4, NT = 512;
     __shared__ __attribute__((aligned(16))) uint16_t tile[TOK * C];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if ((int)blockIdx.x >= nmain) {
@@ -793,11 +759,11 @@ __global__ __launch_bounds__(64 * 32 / RPW, (RPW == 2 || NV <= 5 ? 4 : 2)) void 
         }
         return;
     }
-    // xmap: within each group of 32 workgroups, the 4 tiles of one 128-token span go to workgroups
+    // within each group of 32 workgroups, the 4 tiles of one 128-token span go to workgroups
     // 8 apart (the same XCD, dispatched together), so the column form's 32-B pieces of a 128-B line
     // meet in one L2 instead of leaving four L2s as partial lines
     int t = blockIdx.x;
-    if (xmap && (int)(blockIdx.x | 31) < nmain) t = (blockIdx.x & ~31) + (blockIdx.x & 7) * 4 + ((blockIdx.x >> 3) & 3);
+    if ((int)(blockIdx.x | 31) < nmain) t = (blockIdx.x & ~31) + (blockIdx.x & 7) * 4 + ((blockIdx.x >> 3) & 3);
     const int tok0 = t * TOK;
     // row i + 1 in flight while row i reduces, row i + 2 requested once row i's inputs are dead
     // (clamped rows: unconditional loads).  A branch-free form (zero-selects, buffer stores that drop
@@ -810,15 +776,13 @@ __global__ __launch_bounds__(64 * 32 / RPW, (RPW == 2 || NV <= 5 ? 4 : 2)) void 
         for (int j = 0; j < NV; j++) v[i & 1][j] = x4[lane + 64 * j];
     };
     load(0);
-    if (RPW > 1) load(1);
+    load(1);
     // the LN weight / bias float4s of this lane, once per wave (not a dependent load per row)
     float4 w4[NV], b4[NV];
-    if constexpr (WB) {
 #pragma unroll
-        for (int j = 0; j < NV; j++) {
-            w4[j] = reinterpret_cast<const float4*>(w)[lane + 64 * j];
-            b4[j] = reinterpret_cast<const float4*>(b)[lane + 64 * j];
-        }
+    for (int j = 0; j < NV; j++) {
+        w4[j] = reinterpret_cast<const float4*>(w)[lane + 64 * j];
+        b4[j] = reinterpret_cast<const float4*>(b)[lane + 64 * j];
     }
 #pragma unroll
     for (int i = 0; i < RPW; i++) {
@@ -840,10 +804,7 @@ __global__ __launch_bounds__(64 * 32 / RPW, (RPW == 2 || NV <= 5 ? 4 : 2)) void 
         uint2 hv[NV];
 #pragma unroll
         for (int j = 0; j < NV; j++) {
-            const int k = lane + 64 * j;
-            const float4 y = WB ? ln_vec_y(v[i & 1][j], w4[j], b4[j], m, rs)
-                                : ln_vec_y(v[i & 1][j], reinterpret_cast<const float4*>(w)[k],
-                                           reinterpret_cast<const float4*>(b)[k], m, rs);
+            const float4 y = ln_vec_y(v[i & 1][j], w4[j], b4[j], m, rs);
             hv[j] = make_uint2(pack_bf16x2(y.x, y.y), pack_bf16x2(y.z, y.w));
         }
         if (i + 2 < RPW) load(i + 2);  // row i's inputs are dead: its buffer takes row i + 2
@@ -1134,25 +1095,16 @@ void gemm_fp8(const GemmArgs& a, hipStream_t s) {
     GemmArgs b = a;
     float* slab = nullptr;
     if (a.epi == EPI_F32_ATOMIC) {
-        // the bf16 weight gradients' r06 rule (gemm.hip choose_split_g4): the smallest split filling
-        // >= 80 % of the 256 slots in one round, before the round-5 rule (ViT-H/14 fp8 qkv wgrad 10 -> 3
-        // splits, proj 10 -> 9: 1094 / 1091 vs 1081 / 1075 img/s, two interleaved rounds,
-        // profiles/r06_g4_slots.txt); VIT_F8_SPLIT_RULE=0: the round-5 rule alone
-        static const bool one_round = [] {
-            const char* e = getenv("VIT_F8_SPLIT_RULE");
-            return !(e && e[0] == '0');
-        }();
-        // fill target 45 % (VIT_F8_FILL): ViT-H/14 fp8 80 -> 60 -> 45 -> 35 -> 25 %: 1091 -> 1103 -> 1108 ->
+        // the bf16 weight gradients' rule (gemm.hip choose_split_g4): the smallest split filling the
+        // target share of the 256 slots in one round, before the multi-round rule (ViT-H/14 fp8 qkv wgrad
+        // 10 -> 3 splits, proj 10 -> 9: 1094 / 1091 vs 1081 / 1075 img/s, two interleaved rounds,
+        // profiles/r06_g4_slots.txt).
+        // Fill target 45 %: ViT-H/14 fp8 80 -> 60 -> 45 -> 35 -> 25 %: 1091 -> 1103 -> 1108 ->
         // 1103 -> 1092 img/s (interleaved rounds, profiles/r06_f8_fill.txt): half-filled rounds of fewer
         // splits, the micro-batch streams' kernels beside them
-        static const double fill = [] {
-            const char* e = getenv("VIT_F8_FILL");
-            const int v = e ? atoi(e) : 45;
-            return (v >= 20 && v <= 100 ? v : 45) / 100.0;
-        }();
         split = 0;
-        if (a.splitk <= 0 && one_round) {
-            const double f = a.fill_pct > 0 ? a.fill_pct / 100.0 : fill;
+        if (a.splitk <= 0) {
+            const double f = (a.fill_pct > 0 ? a.fill_pct : 45) / 100.0;
             const int nk = a.K / f8::KB, s1 = (int)((f * 256 + tiles - 1) / tiles);
             if (s1 >= 1 && tiles * s1 <= 256 && nk / s1 >= 16) split = s1;
         }
@@ -1187,7 +1139,7 @@ void gemm_fp8(const GemmArgs& a, hipStream_t s) {
     if (split == 1 && gemm_streaming() && b.epi != EPI_F32_ACC && !epi_aux16(b.epi) && a.K >= 2 * f8::KB &&
         (long long)a.M * a.lda < (1LL << 31) &&
         (long long)a.N * a.ldb < (1LL << 31)) {
-        const int cus = gemm_persist_grid();
+        const int cus = gemm_cu_count();
         const dim3 pg(tiles < cus ? tiles : cus);
         switch (b.epi) {
 #define VIT_CASE(E) \
@@ -1282,13 +1234,8 @@ bool quantize_mx_rowcol_bf16(uint8_t* qr, uint8_t* slr, uint8_t* qc, uint8_t* sl
     const long long rp = mx_rows_padded(R);
     const int cpad = (int)mx_rows_padded(C);
     // 128 columns from C = 2048 (ViT-H/14 micro-batch, tools/bench_quant.py: 3840 columns 64 -> 50 us,
-    // 5120: 88 -> 78 us; 1280: 17.0 vs 17.5 us, kept at 64); VIT_ROWCOL_COLS=64|128 forces one
-    static const int force = [] {
-        const char* e = getenv("VIT_ROWCOL_COLS");
-        return e ? atoi(e) : 0;
-    }();
-    const int cols = force == 64 || force == 128 ? force : (C >= 2048 ? 128 : 64);
-    if (cols == 128 && C % 128 == 0)
+    // 5120: 88 -> 78 us; 1280: 17.0 vs 17.5 us, kept at 64)
+    if (C >= 2048 && C % 128 == 0)
         f8::quantize_mx_rowcol_k<128, 128><<<dim3((unsigned)(rp / 128), cpad / 128), 512, 0, s>>>(
             qr, slr, qc, slc, (const uint16_t*)x, (int)R, C, ldx, (int)(rp / 32), ldqc, (int)tok_off, (int)ntok, cpad / 32);
     else
@@ -1321,41 +1268,24 @@ bool ln_forward_mx(uint8_t* qr, uint8_t* slr, uint8_t* qc, uint8_t* slc, float* 
     }
     const long long rp = mx_rows_padded(R);
     const int rgr = (int)(rp / 32), rgc = (int)(mx_rows_padded(C) / 32);
-    // whole rounds of tiles only (two 80-KiB workgroups per CU at 4 rows per wave, one at 2): 16 448 rows
+    // whole rounds of tiles only (two 80-KiB workgroups per CU): 16 448 rows
     // are 514 tiles for 512 slots, and the 2 of a second round would cost a whole tile time; the rows of
     // a last partial round go one per wave to extra workgroups (row form, bf16 row into the scratch) and
     // their column form comes from a follow-up quantize of those rows
-    static const int rpw_env = [] {
-        const char* e = getenv("VIT_LNMX_RPW");
-        return e && atoi(e) == 2 ? 2 : 4;
-    }();
-    const int ntiles = (int)(rp / 32), slots = gemm_cu_count() * (rpw_env == 2 ? 1 : 2);
+    const int ntiles = (int)(rp / 32), slots = gemm_cu_count() * 2;
     int nmain = ntiles <= slots || !scratch ? ntiles : ntiles / slots * slots;
     if (nmain < ntiles && (long long)nmain * 32 >= R && ntok > (long long)nmain * 32) nmain -= slots;
     const long long r_left = (long long)nmain * 32;  // leftover rows: < 2 rounds of tiles <= ln_mx_scratch_rows()
     uint16_t* ybf = reinterpret_cast<uint16_t*>(scratch);
-    const dim3 g((unsigned)(nmain + (ntiles - nmain) * 32 / (64 * 32 / rpw_env / 64)));
-    static const int xmap = [] {
-        const char* e = getenv("VIT_LNMX_XMAP");
-        return e ? atoi(e) : 1;
-    }();
-    static const bool wb = [] {
-        const char* e = getenv("VIT_LNMX_WB");
-        return !(e && e[0] == '0');
-    }();
-    const int rpw = rpw_env;
+    const dim3 g((unsigned)(nmain + (ntiles - nmain) * 32 / 8));  // leftover rows: one per wave, 8 per workgroup
     switch (C / 256) {
-#define VIT_LAUNCH(NV, WB, RPW) \
-    f8::ln_fwd_mx_k<NV, WB, RPW><<<g, 64 * 32 / RPW, 0, s>>>(qr, slr, qc, slc, mean, rstd, x, w, b, (int)R, rgr, ldqc, \
-                                                             (int)tok_off, (int)ntok, rgc, xmap, nmain, ntiles, ybf)
 #define VIT_CASE(NV) \
     case NV: \
-        if (rpw == 2) { if (wb) VIT_LAUNCH(NV, true, 2); else VIT_LAUNCH(NV, false, 2); } \
-        else { if (wb) VIT_LAUNCH(NV, true, 4); else VIT_LAUNCH(NV, false, 4); } \
+        f8::ln_fwd_mx_k<NV><<<g, 512, 0, s>>>(qr, slr, qc, slc, mean, rstd, x, w, b, (int)R, rgr, ldqc, (int)tok_off, \
+                                              (int)ntok, rgc, nmain, ntiles, ybf); \
         break;
         VIT_CASE(1) VIT_CASE(2) VIT_CASE(3) VIT_CASE(4) VIT_CASE(5) VIT_CASE(6) VIT_CASE(8)
 #undef VIT_CASE
-#undef VIT_LAUNCH
         default: break;
     }
     after_launch("ln_forward_mx");

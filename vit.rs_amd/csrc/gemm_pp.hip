@@ -45,12 +45,6 @@ constexpr int ST_WAVE = 16 * ST_LD * 4;   // 8,448 B: one 16-row pass of a 96 x 
 constexpr int LDS_BYTES = NS * SLOT + 4 * ST_WAVE;
 constexpr int NCHUNK = 24;                // epilogue chunks per wave tile: 6 passes x 4 row groups
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
-#ifndef VIT_PP_EPRIO
-#define VIT_PP_EPRIO 0  // s_setprio of the epilogue group (the main group runs at 1)
-#endif
-#ifndef VIT_PP_NOEPI
-#define VIT_PP_NOEPI 0  // diagnostic compile: no epilogue code (register-pressure experiments)
-#endif
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -504,10 +498,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_pp(GemmParams p) {
             __builtin_amdgcn_sched_barrier(0);
         }
         // ------------------------------------------------- epilogue of tile jj (+ DMA for jj + 2)
-        __builtin_amdgcn_s_setprio(VIT_PP_EPRIO);
+        __builtin_amdgcn_s_setprio(0);  // the epilogue group; the main group runs at 1
         const int m0 = t.tm0 + wm * 96, n0 = t.tn0 + wn * 128;
         if (jj + 1 < my_tiles) {  // beside the other group's tile jj + 1
-            if (!VIT_PP_NOEPI && !(p.no_epi & 1)) {
+            if (!(p.no_epi & 1)) {
                 epilogue<EPI, true>(p, acc, st, lane, m0, n0, I, ebar);
             } else {  // diagnostic main-loop-only timing: the accumulators stay live, nothing stored
 #pragma unroll
@@ -518,7 +512,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_kernel_pp(GemmParams p) {
             }
             dma_intervals(jj + 2);
         } else {  // the last tile: after every other wave's work, no barriers
-            if (!VIT_PP_NOEPI && !(p.no_epi & 1)) {
+            if (!(p.no_epi & 1)) {
                 epilogue<EPI, false>(p, acc, st, lane, m0, n0, 0, bar);
             } else {
 #pragma unroll

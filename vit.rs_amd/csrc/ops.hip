@@ -707,8 +707,7 @@ __global__ void patch_gather_vec_k(bf16_t* __restrict__ out, const bf16_t* __res
 }
 // gather the patch rows of dencoded into [B*NP, C] (TO = float or bf16; TI likewise)
 template <typename TO, typename TI>
-__global__ void patch_gather_k(TO* __restrict__ out, const TI* __restrict__ denc, const uint8_t* __restrict__ lo,
-                               int B, int NP, int C) {
+__global__ void patch_gather_k(TO* __restrict__ out, const TI* __restrict__ denc, int B, int NP, int C) {
     const int T = NP + 1;
     const long long n = (long long)B * NP * C;
     for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n;
@@ -719,8 +718,7 @@ __global__ void patch_gather_k(TO* __restrict__ out, const TI* __restrict__ denc
         const long long src = ((long long)b * T + 1 + p) * C + c;
         const TI v = denc[src];
         if constexpr (sizeof(TO) == sizeof(TI)) out[idx] = v;
-        else if constexpr (sizeof(TO) == 2) out[idx] = f2bf(v);
-        else out[idx] = lo ? lo8_decode(bf2f(v), lo[src]) : bf2f(v);
+        else out[idx] = f2bf(v);
     }
 }
 // dwpe[t,c] += colsum_t[c] = sum_b denc[b,t,c] (a fixed order); colsum_t -> tsum[t][c]
@@ -1090,25 +1088,20 @@ void patch_assemble(float* enc, const float* emb, const float* cls, const float*
 }
 void patch_gather_f32(float* out, const float* denc, int B, int NP, int C, hipStream_t s) {
     const long long n = (long long)B * NP * C;
-    patch_gather_k<float, float><<<grid_for(n, 256), 256, 0, s>>>(out, denc, nullptr, B, NP, C);
+    patch_gather_k<float, float><<<grid_for(n, 256), 256, 0, s>>>(out, denc, B, NP, C);
     after_launch("patch_gather");
 }
 void patch_gather_bf16(bf16_t* out, const float* denc, int B, int NP, int C, hipStream_t s) {
     const long long n = (long long)B * NP * C;
-    patch_gather_k<bf16_t, float><<<grid_for(n, 256), 256, 0, s>>>(out, denc, nullptr, B, NP, C);
+    patch_gather_k<bf16_t, float><<<grid_for(n, 256), 256, 0, s>>>(out, denc, B, NP, C);
     after_launch("patch_gather_bf16");
-}
-void patch_gather_f32(float* out, const bf16_t* denc, const uint8_t* lo, int B, int NP, int C, hipStream_t s) {
-    const long long n = (long long)B * NP * C;
-    patch_gather_k<float, bf16_t><<<grid_for(n, 256), 256, 0, s>>>(out, denc, lo, B, NP, C);
-    after_launch("patch_gather");
 }
 void patch_gather_bf16(bf16_t* out, const bf16_t* denc, int B, int NP, int C, hipStream_t s) {
     const long long n = (long long)B * NP * C;
     if (C % 8 == 0 && al16(out) && al16(denc))
         patch_gather_vec_k<<<grid_for(n / 8, 256), 256, 0, s>>>(out, denc, B, NP, C);
     else
-        patch_gather_k<bf16_t, bf16_t><<<grid_for(n, 256), 256, 0, s>>>(out, denc, nullptr, B, NP, C);
+        patch_gather_k<bf16_t, bf16_t><<<grid_for(n, 256), 256, 0, s>>>(out, denc, B, NP, C);
     after_launch("patch_gather_bf16");
 }
 template <typename TI>

@@ -78,8 +78,6 @@ void transpose_bf16(bf16_t* out, const bf16_t* in, int R, int Cc, int count, lon
                     hipStream_t s);
 void patch_gather_f32(float* out, const float* denc, int B, int NP, int C, hipStream_t s);
 void patch_gather_bf16(bf16_t* out, const float* denc, int B, int NP, int C, hipStream_t s);
-// (bf16 + lo8 input: lo nullable)
-void patch_gather_f32(float* out, const bf16_t* denc, const uint8_t* lo, int B, int NP, int C, hipStream_t s);
 void patch_gather_bf16(bf16_t* out, const bf16_t* denc, int B, int NP, int C, hipStream_t s);
 // dcls += sum_b denc[b,0];  dwpe[t] += sum_b denc[b,t];  dpb += sum_{b,t>0} denc[b,t] — fixed order
 // (no atomics); ws (nullable = thread workspace): T*C floats of per-position sums

@@ -376,7 +376,6 @@ struct Trainer {
     };
     std::vector<LayerActs> la;
     float* encoded = nullptr;
-    bool patch_f32 = false;  // bf16 mode, KP % 8 != 0 and VIT_PATCH_PAD=0: patch embedding on the fp32 GEMM
     // bf16 / fp8 mode, KP % 8 != 0 (ViT-H/14: 588): the patch GEMMs run on the bf16 engine over
     // KPP = KP rounded up to 64 columns: zero-padded im2col rows, a zero-padded bf16 weight copy
     // (refreshed with the transposed copies) and a padded fp32 weight-gradient scratch whose first
@@ -466,10 +465,9 @@ struct Trainer {
     uint8_t* act_q2[4]{};
     uint8_t* act_s2[4]{};
     bool fuse_mx = true;
-    // fp8 weight gradients (VIT_FP8_WGRAD=0: bf16 as before): dout and inp quantized column-wise
+    // fp8 weight gradients: dout and inp quantized column-wise
     // (MX blocks of 32 consecutive tokens: the axis the weight gradient reduces over) into [OC][Kp] /
     // [Cin][Kp] e4m3 rows on the weight-gradient stream, then the MXFP8 engine with K-split slabs
-    bool fp8_wgrad = true;
     bool wt_cols = true;  // fp8: the dgrads' MX weight copy by column-quantizing W (VIT_FP8_WT_COLS=0: transpose + rows)
     QMat wg_a, wg_b;  // column-quantized dout / inp of the running weight gradient (stream-ordered)
     // fused row+column quantization (quantize_mx_rowcol_bf16): the column forms of ln1, atty, ln2
@@ -486,18 +484,14 @@ struct Trainer {
     QMat fchgc, dfchc;
     bool rowcol_on() const { return fp8() && rowcol_ok && ((long long)(B / nmb) * T) % 64 == 0; }
     bool epicol_on() const { return rowcol_on() && fuse_mx && (4 * C) % 64 == 0; }
-    // fp8: LayerNorm forward straight into the MX forms (ln_forward_mx; VIT_FP8_LN_MX=0: bf16 + rowcol)
-    bool ln_mx = true;
-    bool lnmx_on() const { return rowcol_on() && ln_mx && ln_forward_mx_supported(C); }
+    // fp8: LayerNorm forward straight into the MX forms (ln_forward_mx; else bf16 + rowcol), in whole
+    // tiles: a leftover-row path for the last partial round measured 119.70 vs 119.47 ms/step without it
+    // at ViT-H/14 (the other micro-batch stream already fills the partial round)
+    bool lnmx_on() const { return rowcol_on() && ln_forward_mx_supported(C); }
     // fp8: the residual-gradient LayerNorm backwards also write both MX forms of dres2 / dres3
-    // (ln_backward_bf16_stream_mx; VIT_FP8_LNB_MX=0 / option fp8_lnb_mx: the rowcol quantize instead)
-    bool lnb_mx = true;
-    // option fp8_ln_leftover: the LayerNorm -> MX forward's leftover-row path.  Alone 36.4 -> 32.5 us per
-    // ViT-H/14 micro-batch (tools/bench_lnmx.py), in the step 119.70 vs 119.47 ms without it (the other
-    // micro-batch stream already fills the partial round): off
-    bool ln_left = false;
-    uint8_t* lnb_scr[4]{};  // per micro-batch stream: the LayerNorm -> MX kernels' scratch (ln_mx_scratch_bytes)
-    bool lnbmx_on() const { return rowcol_on() && lnb_mx && ln_backward_mx_supported(C); }
+    // (ln_backward_bf16_stream_mx; else the rowcol quantize)
+    uint8_t* lnb_scr[4]{};  // per micro-batch stream: the LayerNorm backward -> MX kernel's scratch
+    bool lnbmx_on() const { return rowcol_on() && ln_backward_mx_supported(C); }
     // the column-form span of micro-batch mb (R rows): the last one carries the padding tokens
     long long mb_ntok(int mb, long long R) const { return mb == nmb - 1 ? kp_tok - (long long)mb * R : R; }
     QMat fchgc_of(int l) const {
@@ -520,12 +514,8 @@ struct Trainer {
     bf16_t* W(int ti, int l = 0) const { return pbf + off[ti * L + l]; }
     // transposed bf16 copy of a layer weight ([Cin][OC]): the dgrad GEMMs read it K-contiguous
     bf16_t* WT(int ti, int l = 0) const { return pbfT + off[ti * L + l]; }
-    bool dgrad_wt = true;  // option "dgrad_transposed": dgrad B operand from pbfT (K-contig)
-    // dgrad B operand: the transposed copy (K-contiguous, ldb = OC) or W itself (N-contiguous)
-    void dgrad_b(GemmArgs& g, int ti, int l, int OC, int Cin) const {
-        if (dgrad_wt) { g.B = WT(ti, l); g.ldb = OC; g.b_kcontig = true; }
-        else { g.B = W(ti, l); g.ldb = Cin; g.b_kcontig = false; }
-    }
+    // dgrad B operand: the transposed copy (K-contiguous, ldb = OC)
+    void dgrad_b(GemmArgs& g, int ti, int l, int OC) const { g.B = WT(ti, l); g.ldb = OC; g.b_kcontig = true; }
 
     void build_layout() {
         compute_layout(C, L, T, KP, NC, canon_size, n_params, off, chunk_off, n_chunks, arena_elems);
@@ -641,39 +631,24 @@ struct Trainer {
             return false;
         }
         if (hipSetDevice(dev) != hipSuccess) { set_error("trainer: hipSetDevice(%d)", dev); return false; }
-        // stream priorities (VIT_STREAM_PRIO overrides): 1 = micro-batch streams high, weight-gradient
-        // stream low; 2 = the reverse; 0 = all equal.  Measured (bench.py, three interleaved rounds each,
-        // profiles/r06_stream_prio.txt): ViT-B/16 bf16 2 vs 0: 7102-7106 vs 7059-7062 img/s (+0.65 %),
-        // 1: -0.2 %; ViT-H/14 fp8 2 vs 0: 1088 vs 1098 img/s (-0.8 %), 1: -2 %.  So 2 in bf16 mode and
-        // 0 in fp8 (a measured choice: which stream's kernels fill the others' partial rounds)
-        int prio_mode = prec == VIT_BF16 ? 2 : 0, p_lo = 0, p_hi = 0;
-        {
-            const char* e = getenv("VIT_STREAM_PRIO");
-            if (e) prio_mode = atoi(e);
-            if (prio_mode) VIT_HIP(hipDeviceGetStreamPriorityRange(&p_lo, &p_hi));
-        }
-        // (3 / 4, A/B only: micro-batch stream 0 high and 1 low, the weight-gradient stream high / low)
-        auto mk_stream = [&](hipStream_t* st, int role) {  // role: 0 = micro-batch 0, 1 = other micro-batch, 2 = wgrad
-            if (!prio_mode) {
-                VIT_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-            } else {
-                bool hi;
-                if (prio_mode == 1) hi = role != 2;
-                else if (prio_mode == 2) hi = role == 2;
-                else hi = role == 0 || (role == 2 && prio_mode == 3);
-                VIT_HIP(hipStreamCreateWithPriority(st, hipStreamNonBlocking, hi ? p_hi : p_lo));
-            }
+        // stream priorities: bf16 mode runs the weight-gradient stream high and the micro-batch streams
+        // low, fp8 mode all equal.  Measured (bench.py, three interleaved rounds each,
+        // profiles/r06_stream_prio.txt): ViT-B/16 bf16 wgrad-high vs equal: 7102-7106 vs 7059-7062 img/s
+        // (+0.65 %), micro-batch-high: -0.2 %; ViT-H/14 fp8 wgrad-high vs equal: 1088 vs 1098 img/s
+        // (-0.8 %), micro-batch-high: -2 % (which stream's kernels fill the others' partial rounds)
+        const bool prio = prec == VIT_BF16;
+        int p_lo = 0, p_hi = 0;
+        if (prio) VIT_HIP(hipDeviceGetStreamPriorityRange(&p_lo, &p_hi));
+        auto mk_stream = [&](hipStream_t* st, bool wgrad) {
+            if (!prio) VIT_HIP(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+            else VIT_HIP(hipStreamCreateWithPriority(st, hipStreamNonBlocking, wgrad ? p_hi : p_lo));
         };
-        mk_stream(&s, 0);
+        mk_stream(&s, false);
         VIT_HIP(hipStreamCreateWithFlags(&s_comm, hipStreamNonBlocking));
-        mk_stream(&s2, 2);
-        {
-            const char* e = getenv("VIT_BWD_STREAMS");
-            two_streams = !(e && atoi(e) == 1);
-        }
+        mk_stream(&s2, true);
         for (auto& e : bev) VIT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ms[0] = s;
-        for (int k = 1; k < MAXMB; k++) mk_stream(&ms[k], 1);
+        for (int k = 1; k < MAXMB; k++) mk_stream(&ms[k], false);
         for (auto& row : mev)
             for (auto& e : row) VIT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         VIT_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
@@ -732,19 +707,12 @@ struct Trainer {
             }
             // a patch whose im2col row (3*P*P) is not a multiple of 8 bf16 (ViT-H/14: 588) cannot
             // feed the bf16 GEMM's 16-B loads as it is: padded to KPP columns (the fp32 GEMM from
-            // the fp32 master weights with VIT_PATCH_PAD=0, the round-2 form: 3 ms/step at H/14)
-            const char* pp = getenv("VIT_PATCH_PAD");
-            patch_f32 = KP % 8 != 0 && pp && pp[0] == '0';
-            patch_pad = KP % 8 != 0 && !patch_f32;
+            // the fp32 master weights, the earlier form, cost 3 ms/step at H/14)
+            patch_pad = KP % 8 != 0;
             KPP = patch_pad ? (KP + 63) / 64 * 64 : KP;
             pbf = alloc<bf16_t>(arena_elems);
             pbfT = alloc<bf16_t>(arena_elems);
-            if (patch_f32) {
-                patches_f = alloc<float>((long long)B * NP * KP);
-                dpatch_f = alloc<float>((long long)B * NP * C);
-            } else {
-                patches_bf = alloc<bf16_t>((long long)B * NP * KPP);
-            }
+            patches_bf = alloc<bf16_t>((long long)B * NP * KPP);
             if (patch_pad) {
                 wpatch_pad = alloc<bf16_t>((long long)C * KPP);
                 dwpatch_pad = alloc<float>((long long)C * KPP);
@@ -789,7 +757,7 @@ struct Trainer {
             dfch = alloc<bf16_t>(BT * 4 * C);
             datty = alloc<bf16_t>(BT * C);
             dqkv = alloc<bf16_t>(BT * 3 * C);
-            if (!patch_f32) dpatch_bf = alloc<bf16_t>((long long)B * NP * C);
+            dpatch_bf = alloc<bf16_t>((long long)B * NP * C);
             // slabs: <= 32 splits of the largest weight gradient (4C x C)
             gemm_ws_bytes = (size_t)32 * 4 * C * (size_t)std::max(C, KP) * sizeof(float);
             gemm_ws = alloc<float>((long long)(gemm_ws_bytes / sizeof(float)));
@@ -831,36 +799,28 @@ struct Trainer {
                 fuse_mx = !(fe && fe[0] == '0');
                 const char* wc = getenv("VIT_FP8_WT_COLS");
                 wt_cols = !(wc && wc[0] == '0') && C % 64 == 0;
-                const char* fw = getenv("VIT_FP8_WGRAD");
-                fp8_wgrad = !(fw && fw[0] == '0') && C % 64 == 0;
-                if (fp8_wgrad) {
-                    const long long kp = mx_cols_kp(BT);
-                    wg_a.q = alloc<uint8_t>(4LL * C * kp);
-                    wg_a.s = alloc<uint8_t>((long long)mx_scale_bytes(4LL * C, (int)kp));
-                    wg_b.q = alloc<uint8_t>(4LL * C * kp);
-                    wg_b.s = alloc<uint8_t>((long long)mx_scale_bytes(4LL * C, (int)kp));
-                    const char* lx = getenv("VIT_FP8_LN_MX");
-                    ln_mx = !(lx && lx[0] == '0');
-                    const char* lbx = getenv("VIT_FP8_LNB_MX");
-                    lnb_mx = !(lbx && lbx[0] == '0');
-                    const char* rc = getenv("VIT_FP8_ROWCOL");
-                    rowcol_ok = !(rc && rc[0] == '0');
-                    kp_tok = kp;
-                    if (rowcol_ok) {
-                        for (int k = 0; k < 3; k++) {
-                            actc[k].q = alloc<uint8_t>((long long)L * C * kp);
-                            actc[k].s = alloc<uint8_t>((long long)L * mx_scale_bytes(C, (int)kp));
-                            const long long w = k == 2 ? 3LL * C : C;
-                            dcol[k].q = alloc<uint8_t>(w * kp);
-                            dcol[k].s = alloc<uint8_t>((long long)mx_scale_bytes(w, (int)kp));
-                        }
-                        fchgc.q = alloc<uint8_t>((long long)L * 4 * C * kp);
-                        fchgc.s = alloc<uint8_t>((long long)L * mx_scale_bytes(4LL * C, (int)kp));
-                        dfchc.q = alloc<uint8_t>(4LL * C * kp);
-                        dfchc.s = alloc<uint8_t>((long long)mx_scale_bytes(4LL * C, (int)kp));
-                        if (ln_backward_mx_supported(C) || ln_forward_mx_supported(C))
-                            for (int k = 0; k < MAXMB; k++) lnb_scr[k] = alloc<uint8_t>((long long)ln_mx_scratch_bytes(C));
+                const long long kp = mx_cols_kp(BT);
+                wg_a.q = alloc<uint8_t>(4LL * C * kp);
+                wg_a.s = alloc<uint8_t>((long long)mx_scale_bytes(4LL * C, (int)kp));
+                wg_b.q = alloc<uint8_t>(4LL * C * kp);
+                wg_b.s = alloc<uint8_t>((long long)mx_scale_bytes(4LL * C, (int)kp));
+                const char* rc = getenv("VIT_FP8_ROWCOL");
+                rowcol_ok = !(rc && rc[0] == '0');
+                kp_tok = kp;
+                if (rowcol_ok) {
+                    for (int k = 0; k < 3; k++) {
+                        actc[k].q = alloc<uint8_t>((long long)L * C * kp);
+                        actc[k].s = alloc<uint8_t>((long long)L * mx_scale_bytes(C, (int)kp));
+                        const long long w = k == 2 ? 3LL * C : C;
+                        dcol[k].q = alloc<uint8_t>(w * kp);
+                        dcol[k].s = alloc<uint8_t>((long long)mx_scale_bytes(w, (int)kp));
                     }
+                    fchgc.q = alloc<uint8_t>((long long)L * 4 * C * kp);
+                    fchgc.s = alloc<uint8_t>((long long)L * mx_scale_bytes(4LL * C, (int)kp));
+                    dfchc.q = alloc<uint8_t>(4LL * C * kp);
+                    dfchc.s = alloc<uint8_t>((long long)mx_scale_bytes(4LL * C, (int)kp));
+                    if (ln_backward_mx_supported(C))
+                        for (int k = 0; k < MAXMB; k++) lnb_scr[k] = alloc<uint8_t>((long long)ln_backward_mx_scratch_bytes(C));
                 }
             }
         } else {
@@ -939,12 +899,11 @@ struct Trainer {
         if (s2) (void)hipStreamDestroy(s2);
     }
 
-    // side pre-work (option pre_side, bf16 / fp8 with two streams, timing off): the gradient-arena
+    // side pre-work (bf16 / fp8 with two streams, timing off): the gradient-arena
     // clear and the transposed weight copies run on s2 beside the forward instead of ahead of it on s.
     // pre_side_begin orders s2 after everything enqueued on s so far; pre_side_end records EV_PRE,
     // which s waits for before the backward's first gradient write (backward_bf16)
-    bool pre_side = true;
-    bool pre_side_on() const { return pre_side && two_streams && lowp() && !timing && s2; }
+    bool pre_side_on() const { return two_streams && lowp() && !timing && s2; }
     hipStream_t pre_side_begin() {
         VIT_HIP(hipEventRecord(bev[EV_PRE_IN], s));
         VIT_HIP(hipStreamWaitEvent(s2, bev[EV_PRE_IN], 0));
@@ -1096,7 +1055,7 @@ struct Trainer {
     }
     // layer l's fcproj dgrad of micro-batch mb into d1: full size (false), or (last_cls_bwd = 2, last block)
     // gathered on the CLS rows when T >= 128, the full-size call would run on the 256x256 engine (not the
-    // ping-pong engine, whose partial rows are 96 tall), the dgrads read the transposed weights and the fc
+    // ping-pong engine, whose partial rows are 96 tall) and the fc
     // weight gradient of the step skips the K-steps without a CLS row (it then reads dfch in the CLS rows'
     // 32-row blocks only).  Sets fcb_rows (the full-size call's partial rows per micro-batch).
     bool lc_d1_gathered(int l, int mb, const bf16_t* dres3, GemmArgs& d1) {
@@ -1104,12 +1063,12 @@ struct Trainer {
         const long long R = (long long)Bm * T, r0 = mb * R;
         LayerActs& a = la[l];
         d1 = GemmArgs();
-        d1.A = dres3 + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C, 4 * C);
+        d1.A = dres3 + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C);
         d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
         d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
         fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
         d1.colsum_part = sg_rows(l, sg_fcb) + (long long)mb * fcb_rows * 4 * C;
-        if (!(last_cls_on() && lc_bwd >= 2 && l == L - 1 && T >= 128 && R >= 256 && dgrad_wt)) return false;
+        if (!(last_cls_on() && lc_bwd >= 2 && l == L - 1 && T >= 128 && R >= 256)) return false;
         GemmArgs g = d1;
         g.M = Bm; g.lda = (long long)T * C; g.ldc = (long long)T * 4 * C; g.ldaux = (long long)T * 4 * C;
         g.rows_gathered = true; g.colsum_row_period = T;
@@ -1162,12 +1121,7 @@ struct Trainer {
     // The engine's rule stops at >= 8 K-steps per split (192-256 workgroups of 12-16 dependent
     // K-steps: 20-47 us per GEMM at B = 256, on the critical path between forward and backward);
     // bounded by the slab workspace
-    bool head_sk = true;  // option head_splitk (A/B): 0 = the engine's split rule
-    // option patch_tail (A/B): the patch embedding backward after the join with its weight gradient
-    // split for 80 % of the slots and the small gradients on s2 beside it (0: 45 %, all on s)
-    bool patch_tail = true;
     int head_split(int M, int N, int K) const {
-        if (!head_sk) return 0;
         int sp = std::min(16, std::max(1, K / 64));
         while (sp > 1 && (size_t)sp * M * N * sizeof(float) > gemm_ws_bytes) sp--;
         return sp;
@@ -1254,12 +1208,7 @@ struct Trainer {
             GemmArgs a;
             a.C = emb_tmp + img0 * NP * C; a.ldc = C; a.bias = P(P_PATCH_B);
             a.M = Bm * NP; a.N = C; a.K = KP; a.epi = EPI_F32_STORE;
-            if (patch_f32) {
-                im2col_f32(patches_f + img0 * NP * KP, pixels + img0 * 3 * cfg.img * cfg.img, Bm, cfg.img,
-                           cfg.patch, st);
-                a.A = patches_f + img0 * NP * KP; a.lda = KP; a.B = P(P_PATCH_W); a.ldb = KP;
-                gemm_f32(a, st);
-            } else if (patch_pad) {
+            if (patch_pad) {
                 im2col_pad_bf16(patches_bf + img0 * NP * KPP, pixels + img0 * 3 * cfg.img * cfg.img, Bm, cfg.img,
                                 cfg.patch, KPP, st);
                 a.A = patches_bf + img0 * NP * KPP; a.lda = KPP; a.B = wpatch_pad; a.ldb = KPP; a.K = KPP;
@@ -1293,8 +1242,7 @@ struct Trainer {
                 tbeg(TC_LN_FWD, 0, st);
                 if (lm)  // ln1 only in its two MX forms (the qkv GEMM's A operand, the qkv wgrad's B)
                     ln_forward_mx(act_q[mb], act_s[mb], c_ln1.q, c_ln1.s, a.ln1_mean + r0, a.ln1_rstd + r0, x,
-                                  P(P_LN1W, l), P(P_LN1B, l), R, C, kp_tok, r0, mb_ntok(mb, R), st,
-                                  ln_left ? lnb_scr[mb] : nullptr);
+                                  P(P_LN1W, l), P(P_LN1B, l), R, C, kp_tok, r0, mb_ntok(mb, R), st, nullptr);
                 else
                     ln_forward_bf16(a.ln1 + r0 * C, a.ln1_mean + r0, a.ln1_rstd + r0, x, P(P_LN1W, l), P(P_LN1B, l), R, C, st);
                 tend();
@@ -1317,8 +1265,7 @@ struct Trainer {
                 tbeg(TC_LN_FWD, 0, st);
                 if (lm)
                     ln_forward_mx(act_q[mb], act_s[mb], c_ln2.q, c_ln2.s, a.ln2_mean + r0, a.ln2_rstd + r0,
-                                  a.res2 + r0 * C, P(P_LN2W, l), P(P_LN2B, l), R, C, kp_tok, r0, mb_ntok(mb, R), st,
-                                  ln_left ? lnb_scr[mb] : nullptr);
+                                  a.res2 + r0 * C, P(P_LN2W, l), P(P_LN2B, l), R, C, kp_tok, r0, mb_ntok(mb, R), st, nullptr);
                 else
                     ln_forward_bf16(a.ln2 + r0 * C, a.ln2_mean + r0, a.ln2_rstd + r0, a.res2 + r0 * C, P(P_LN2W, l),
                                     P(P_LN2B, l), Mr, C, st, rs);
@@ -1363,7 +1310,7 @@ struct Trainer {
                 VIT_HIP(hipStreamWaitEvent(s2, mev[mb][ready], 0));
             }
         }
-        if (fp8() && fp8_wgrad) {
+        if (fp8()) {
             const long long kp = mx_cols_kp(BT);
             const QMat qa = dout_c ? *dout_c : wg_a, qb = inp_c ? *inp_c : wg_b;
             if (!dout_c || !inp_c) {
@@ -1497,7 +1444,7 @@ struct Trainer {
                 if (lc && d1_clean && !ec && lc_d1_gathered(l, mb, sA, d1g)) {
                     d1 = d1g;
                 } else {
-                    d1.A = sA + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C, 4 * C);
+                    d1.A = sA + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C);
                     d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
                     d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
                     fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
@@ -1519,7 +1466,7 @@ struct Trainer {
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d2;
-                d2.A = dfch + r0 * 4 * C; d2.lda = rs * 4 * C; dgrad_b(d2, P_FCW, l, 4 * C, C);
+                d2.A = dfch + r0 * 4 * C; d2.lda = rs * 4 * C; dgrad_b(d2, P_FCW, l, 4 * C);
                 d2.C = dln_bf + r0 * C; d2.ldc = rs * C; d2.M = Mr; d2.N = C; d2.K = 4 * C; d2.epi = EPI_BF16_STORE;
                 d2.rows_gathered = lcg;
                 gemm_w(TC_FC_DGRAD, d2, P_FCW, l, true, mb, ms[mb], fuse_mx ? PRE_EPI : PRE_NONE);
@@ -1553,7 +1500,7 @@ struct Trainer {
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d3;
-                d3.A = sB + r0 * C; d3.lda = rs * C; dgrad_b(d3, P_ATTPROJW, l, C, C);
+                d3.A = sB + r0 * C; d3.lda = rs * C; dgrad_b(d3, P_ATTPROJW, l, C);
                 d3.C = datty + r0 * C; d3.ldc = rs * C; d3.M = Mr; d3.N = C; d3.K = C; d3.epi = EPI_BF16_STORE;
                 d3.rows_gathered = lcg;
                 gemm_w(TC_PROJ_DGRAD, d3, P_ATTPROJW, l, true, mb, ms[mb], lbm ? PRE_LN : PRE_NONE, false,
@@ -1573,7 +1520,7 @@ struct Trainer {
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d4;
-                d4.A = dqkv + r0 * 3 * C; d4.lda = 3 * C; dgrad_b(d4, P_QKVW, l, 3 * C, C);
+                d4.A = dqkv + r0 * 3 * C; d4.lda = 3 * C; dgrad_b(d4, P_QKVW, l, 3 * C);
                 d4.C = dln_bf + r0 * C; d4.ldc = C; d4.M = (int)R; d4.N = C; d4.K = 3 * C; d4.epi = EPI_BF16_STORE;
                 gemm_w(TC_QKV_DGRAD, d4, P_QKVW, l, true, mb, ms[mb], PRE_NONE, false, rc ? &dcol[2] : nullptr, EV_DQKV);
                 // ln1 backward: dres = dres2 + LN1'(dln1); fcproj_b of layer l-1 += colsum(dres)
@@ -1614,37 +1561,29 @@ struct Trainer {
         tbeg(TC_PATCH_BWD, 2.0 * B * NP * (double)KP * C);
         // cls / position / patch-bias gradients (psg: three small kernels, 43 us) on s2 beside the
         // patch weight gradient on s; s waits for them before the chunk is final
-        const bool psg_side = two_streams && lowp() && patch_tail;
+        const bool psg_side = two_streams && lowp();
         if (psg_side) {
             VIT_HIP(hipEventRecord(bev[EV_SG], s));
             VIT_HIP(hipStreamWaitEvent(s2, bev[EV_SG], 0));
             patch_small_grads(G(P_CLS), G(P_WPE), G(P_PATCH_B), rbA, loA, B, T, C, s2, pos_sums, psg_part);
             VIT_HIP(hipEventRecord(bev[EV_JOIN], s2));
         }
-        if (patch_f32) {
-            patch_gather_f32(dpatch_f, rbA, loA, B, NP, C, s);
-            GemmArgs w;
-            w.A = dpatch_f; w.lda = C; w.a_kcontig = false; w.B = patches_f; w.ldb = KP; w.b_kcontig = false;
-            w.C = G(P_PATCH_W); w.ldc = KP; w.M = C; w.N = KP; w.K = B * NP; w.epi = EPI_F32_ATOMIC;
-            gemm_f32(w, s);
-        } else {
-            patch_gather_bf16(dpatch_bf, rbA, B, NP, C, s);
-            GemmArgs w;
-            w.A = dpatch_bf; w.lda = C; w.a_kcontig = false;
-            w.B = patches_bf; w.ldb = KPP; w.b_kcontig = false;
-            w.C = G(P_PATCH_W); w.ldc = KP; w.M = C; w.N = KP; w.K = B * NP; w.epi = EPI_F32_ATOMIC;
-            w.ws = gemm_ws; w.ws_bytes = gemm_ws_bytes;
-            // after the join nothing but the small-gradient kernels runs beside it: split-K for 80 %
-            // of the slots (the 45 % default leaves half the CUs idle: 102 us with 234 workgroups)
-            w.fill_pct = patch_tail ? 80 : 0;
-            if (patch_pad) {  // dW over KPP columns into the scratch, then its first KP columns into G
-                VIT_HIP(hipMemsetAsync(dwpatch_pad, 0, (size_t)C * KPP * 4, s));
-                w.C = dwpatch_pad; w.ldc = KPP; w.N = KPP;
-            }
-            gemm_bf16(w, s);
-            if (patch_pad)
-                add_cols_k<<<grid_for((long long)C * KP, 256), 256, 0, s>>>(G(P_PATCH_W), dwpatch_pad, C, KP, KPP);
+        patch_gather_bf16(dpatch_bf, rbA, B, NP, C, s);
+        GemmArgs w;
+        w.A = dpatch_bf; w.lda = C; w.a_kcontig = false;
+        w.B = patches_bf; w.ldb = KPP; w.b_kcontig = false;
+        w.C = G(P_PATCH_W); w.ldc = KP; w.M = C; w.N = KP; w.K = B * NP; w.epi = EPI_F32_ATOMIC;
+        w.ws = gemm_ws; w.ws_bytes = gemm_ws_bytes;
+        // after the join nothing but the small-gradient kernels runs beside it: split-K for 80 %
+        // of the slots (the 45 % default leaves half the CUs idle: 102 us with 234 workgroups)
+        w.fill_pct = 80;
+        if (patch_pad) {  // dW over KPP columns into the scratch, then its first KP columns into G
+            VIT_HIP(hipMemsetAsync(dwpatch_pad, 0, (size_t)C * KPP * 4, s));
+            w.C = dwpatch_pad; w.ldc = KPP; w.N = KPP;
         }
+        gemm_bf16(w, s);
+        if (patch_pad)
+            add_cols_k<<<grid_for((long long)C * KP, 256), 256, 0, s>>>(G(P_PATCH_W), dwpatch_pad, C, KP, KPP);
         if (psg_side)
             VIT_HIP(hipStreamWaitEvent(s, bev[EV_JOIN], 0));
         else
@@ -3042,25 +2981,10 @@ int vit_trainer_set_option(vit_trainer_t* h, const char* name, int value) {
     if (n == "microbatch") {
         t.mb_want = value;
         t.nmb = t.pick_nmb(value);
-    } else if (n == "dgrad_transposed") {
-        t.dgrad_wt = value != 0;
-    } else if (n == "fp8_ln_mx") {  // fp8: LayerNorm forward into the MX forms (default 1)
-        t.ln_mx = value != 0;
-    } else if (n == "fp8_ln_leftover") {  // fp8: LayerNorm -> MX forward, last partial round as rows (default 0)
-        t.ln_left = value != 0;
     } else if (n == "ema_fused") {  // 0: EMA as ema_update launches behind the un-fused optimizer kernels (A/B)
         t.ema_fused = value != 0;
     } else if (n == "early_sgd") {  // one GPU: SGD per finished gradient chunk inside train_step (default: fp8 mode only)
         t.early_sgd = value < 0 ? -1 : value != 0;
-    } else if (n == "pre_side") {  // bf16 / fp8: gradient clear + transposed weights on s2 beside the forward (default 1)
-        t.pre_side_wait();
-        t.pre_side = value != 0;
-    } else if (n == "patch_tail") {  // bf16 / fp8: patch embedding backward tail, see Trainer::patch_tail (default 1)
-        t.patch_tail = value != 0;
-    } else if (n == "head_splitk") {  // bf16 / fp8: the head GEMMs' split-K at ~4 K-steps per item (default 1)
-        t.head_sk = value != 0;
-    } else if (n == "fp8_lnb_mx") {  // fp8: the residual-gradient LayerNorm backwards write dres' MX forms (default 1)
-        t.lnb_mx = value != 0;
     } else if (n == "clip_overlap") {  // gradient clipping: partial sums per chunk beside the backward (1), at step time (0), auto (-1)
         t.clip_overlap = value < 0 ? -1 : value != 0;
     } else if (n == "last_cls") {  // bf16: the last block's row-wise ops after attention on the CLS rows only (default 1)
