@@ -193,17 +193,9 @@ size_t mx_scale_bytes(long long rows, int K);
 // LayerNorm forward into both MX forms (no bf16 tensor): qr/slr as quantize_mx_rowcol_bf16's row
 // form of ln_forward_bf16's output, qc/slc its column form over [tok_off, tok_off + ntok)
 bool ln_forward_mx_supported(int C);
-// LayerNorm backward of the bf16 + lo8 residual-gradient stream (as ln_backward_bf16_stream, part rows
-// [ln_bwd_blocks(R)][2C | 3C] or, part == nullptr, reduced into dw / db / dres_colsum) plus both MX
-// forms of its bf16 plane (as quantize_mx_rowcol_bf16); C a multiple of 256 up to 1280
+// the MX form of the residual-gradient stream's LayerNorm backward (ops_internal.h LnbArgs): the widths it
+// takes and the bytes of its scratch
 bool ln_backward_mx_supported(int C);
-bool ln_backward_bf16_stream_mx(bf16_t* dres_out, uint8_t* lo_out, const bf16_t* dres_in, const uint8_t* lo_in,
-                                float* dw, float* db, float* dres_colsum, const bf16_t* dout, const float* inp,
-                                const float* w, const float* mean, const float* rstd, long long R, int C,
-                                hipStream_t s, float* part, uint8_t* qr, uint8_t* slr, uint8_t* qc, uint8_t* slc,
-                                long long ldqc, long long tok_off, long long ntok, uint8_t* scratch);
-// bytes of the scratch ln_backward_bf16_stream_mx needs (nullptr there: the thread workspace; a caller
-// with work in flight on other streams passes its own)
 size_t ln_backward_mx_scratch_bytes(int C);
 // scratch: ln_mx_scratch_bytes(C) (the last partial round's rows; nullptr: no leftover path, every
 // tile through the LDS-tile kernel)

@@ -872,7 +872,7 @@ __global__ __launch_bounds__(512, (NV <= 5 ? 4 : 2)) void ln_fwd_mx_k(uint8_t* _
 // ln_fwd_mx_k).  At the end the 8 waves' partials are summed in wave order into the workgroup's
 // partial row part[blockIdx.x][2C | 3C] (dw | db | dsum); rows gridDim.x .. nparts-1 are zeroed, so
 // the caller reduces the same nparts rows as for ln_bwd_vec_k.  hi / lo and both MX forms equal
-// ln_backward_bf16_stream + quantize_mx_rowcol_bf16 byte for byte; the partial sums group rows
+// ln_backward_stream + quantize_mx_rowcol_bf16 byte for byte; the partial sums group rows
 // differently (a deterministic fixed order, not the same fp32 association).
 struct LnbMx {
     bf16_t* hi_out;
@@ -1301,23 +1301,24 @@ bool ln_forward_mx(uint8_t* qr, uint8_t* slr, uint8_t* qc, uint8_t* slc, float* 
 }
 bool ln_backward_mx_supported(int C) { return C % 256 == 0 && C >= 256 && C <= 1280; }
 size_t ln_backward_mx_scratch_bytes(int C) { return ln_mx_scratch_bytes(C); }
-bool ln_backward_bf16_stream_mx(bf16_t* dres_out, uint8_t* lo_out, const bf16_t* dres_in, const uint8_t* lo_in,
-                                float* dw, float* db, float* dres_colsum, const bf16_t* dout, const float* inp,
-                                const float* w, const float* mean, const float* rstd, long long R, int C,
-                                hipStream_t s, float* part, uint8_t* qr, uint8_t* slr, uint8_t* qc, uint8_t* slc,
-                                long long ldqc, long long tok_off, long long ntok, uint8_t* scratch) {
+bool ln_backward_stream_mx(const LnbArgs& a, hipStream_t s) {
+    const long long R = a.rows, ntok = a.ntok;
+    const int C = a.C;
     if (R <= 0) return true;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (!ln_backward_mx_supported(C) || !dres_out || !lo_out || !dres_in || !lo_in || ldqc % 16 || tok_off % 64 ||
-        tok_off < 0 || ntok < R || ntok > mx_cols_kp(R) || tok_off + ntok > ldqc || !al16(dres_out) || !al16(dres_in) ||
-        !al16(dout) || !al16(inp) || !al16(w) || !al16(qr) || !al16(qc) || (((uintptr_t)lo_in | (uintptr_t)lo_out) & 3) ||
-        R >= (1LL << 30) || ldqc >= (1LL << 31)) {
+    if (!ln_backward_mx_supported(C) || !a.dres_out || !a.lo_out || !a.dres_in || !a.lo_in || a.ldqc % 16 ||
+        a.tok_off % 64 || a.tok_off < 0 || ntok < R || ntok > mx_cols_kp(R) || a.tok_off + ntok > a.ldqc ||
+        !al16(a.dres_out) || !al16(a.dres_in) || !al16(a.dout) || !al16(a.inp) || !al16(a.w) || !al16(a.qr) ||
+        !al16(a.qc) || (((uintptr_t)a.lo_in | (uintptr_t)a.lo_out) & 3) || R >= (1LL << 30) || a.ldqc >= (1LL << 31)) {
         set_error("layernorm_backward_mx: C in 256 .. 1280 (multiple of 256), tok_off %% 64, R <= ntok <= R rounded "
-                  "to 64, aligned planes required (C=%d R=%lld tok_off=%lld ntok=%lld ldqc=%lld)", C, R, tok_off, ntok, ldqc);
+                  "to 64, aligned planes required (C=%d R=%lld tok_off=%lld ntok=%lld ldqc=%lld)", C, R, a.tok_off, ntok,
+                  a.ldqc);
         return false;
     }
-    const int nsum = dres_colsum ? 3 * C : 2 * C, nparts = ln_bwd_blocks(R);
-    const bool reduce = part == nullptr;
+    const int nsum = a.dres_colsum ? 3 * C : 2 * C, nparts = ln_bwd_blocks(R);
+    const bool reduce = a.part == nullptr;
+    float* part = a.part;
+    uint8_t* scratch = a.scratch;
     const size_t part_bytes = ((size_t)nparts * nsum * sizeof(float) + 255) / 256 * 256;
     if (reduce || !scratch) {  // the C-ABI path: partial rows and / or the scratch from the thread workspace
         char* ws = (char*)workspace(part_bytes + (scratch ? 0 : ln_backward_mx_scratch_bytes(C)));
@@ -1325,30 +1326,30 @@ bool ln_backward_bf16_stream_mx(bf16_t* dres_out, uint8_t* lo_out, const bf16_t*
         if (reduce) part = (float*)ws;
         if (!scratch) scratch = (uint8_t*)(ws + part_bytes);
     }
-    f8::LnbMx a;
-    a.hi_out = dres_out; a.lo_out = lo_out; a.hi_in = dres_in; a.lo_in = lo_in;
-    a.dout = dout; a.inp = inp; a.w = w; a.mean = mean; a.rstd = rstd;
-    a.part = part; a.nsum = nsum; a.nparts = nparts;
-    a.qr = qr; a.slr = slr; a.qc = qc; a.slc = slc;
+    f8::LnbMx k;
+    k.hi_out = a.dres_out; k.lo_out = a.lo_out; k.hi_in = a.dres_in; k.lo_in = a.lo_in;
+    k.dout = a.dout; k.inp = a.inp; k.w = a.w; k.mean = a.mean; k.rstd = a.rstd;
+    k.part = part; k.nsum = nsum; k.nparts = nparts;
+    k.qr = a.qr; k.slr = a.slr; k.qc = a.qc; k.slc = a.slc;
     const long long rp = mx_rows_padded(R);
-    a.R = (int)R; a.ntiles = (int)(rp / 32); a.rgr_tot = (int)(rp / 32);
-    a.tok_off = (int)tok_off; a.ntok = (int)ntok; a.rgc_tot = (int)(mx_rows_padded(C) / 32); a.ldqc = ldqc;
+    k.R = (int)R; k.ntiles = (int)(rp / 32); k.rgr_tot = (int)(rp / 32);
+    k.tok_off = (int)a.tok_off; k.ntok = (int)ntok; k.rgc_tot = (int)(mx_rows_padded(C) / 32); k.ldqc = a.ldqc;
     // one 8-wave workgroup per CU (160 KiB of LDS at C = 1280), persistent over the 32-token tiles.
     // Whole rounds of tiles only (nmain, a multiple of g): the tiles of a last partial round would
     // leave every other CU idle for a tile time (16 448 rows: 514 tiles on 256 CUs), so their rows are
     // spread one per wave over all workgroups and their column form comes from a follow-up quantize.
-    const int g = std::min(std::min(a.ntiles, gemm_cu_count()), nparts);
-    int nmain = a.ntiles / g * g;
+    const int g = std::min(std::min(k.ntiles, gemm_cu_count()), nparts);
+    int nmain = k.ntiles / g * g;
     // the follow-up needs at least one real row (it writes the padding tokens' zero blocks only then)
-    if (nmain < a.ntiles && (long long)nmain * 32 >= R && ntok > (long long)nmain * 32) nmain -= g;
-    a.nmain = nmain;
+    if (nmain < k.ntiles && (long long)nmain * 32 >= R && ntok > (long long)nmain * 32) nmain -= g;
+    k.nmain = nmain;
     const long long r_left = (long long)nmain * 32;
     switch (C / 256) {
-        case 1: f8::ln_bwd_mx_k<1><<<g, 512, 0, s>>>(a); break;
-        case 2: f8::ln_bwd_mx_k<2><<<g, 512, 0, s>>>(a); break;
-        case 3: f8::ln_bwd_mx_k<3><<<g, 512, 0, s>>>(a); break;
-        case 4: f8::ln_bwd_mx_k<4><<<g, 512, 0, s>>>(a); break;
-        default: f8::ln_bwd_mx_k<5><<<g, 512, 0, s>>>(a); break;
+        case 1: f8::ln_bwd_mx_k<1><<<g, 512, 0, s>>>(k); break;
+        case 2: f8::ln_bwd_mx_k<2><<<g, 512, 0, s>>>(k); break;
+        case 3: f8::ln_bwd_mx_k<3><<<g, 512, 0, s>>>(k); break;
+        case 4: f8::ln_bwd_mx_k<4><<<g, 512, 0, s>>>(k); break;
+        default: f8::ln_bwd_mx_k<5><<<g, 512, 0, s>>>(k); break;
     }
     after_launch("layernorm_backward_mx");
     count_hit(VIT_HIT_LNB_MX);
@@ -1358,14 +1359,14 @@ bool ln_backward_bf16_stream_mx(bf16_t* dres_out, uint8_t* lo_out, const bf16_t*
             return false;
         }
         const long long rs = R - r_left;
-        if (!quantize_mx_rowcol_bf16(scratch, scratch + ((rs * C + 255) / 256 * 256), qc, slc, dres_out + r_left * C, rs,
-                                     C, C, ldqc, tok_off + r_left, ntok - r_left, s))
+        if (!quantize_mx_rowcol_bf16(scratch, scratch + ((rs * C + 255) / 256 * 256), a.qc, a.slc,
+                                     a.dres_out + r_left * C, rs, C, C, a.ldqc, a.tok_off + r_left, ntok - r_left, s))
             return false;
     }
     if (reduce) {
-        const RowsJob jobs[3] = {{dw, part, nparts, nsum, C}, {db, part + C, nparts, nsum, C},
-                                 {dres_colsum, part + 2 * C, nparts, nsum, C}};
-        rows_reduce_add(jobs, dres_colsum ? 3 : 2, s);
+        const RowsJob jobs[3] = {{a.dw, part, nparts, nsum, C}, {a.db, part + C, nparts, nsum, C},
+                                 {a.dres_colsum, part + 2 * C, nparts, nsum, C}};
+        rows_reduce_add(jobs, a.dres_colsum ? 3 : 2, s);
     }
     return true;
 }
@@ -1400,20 +1401,23 @@ void quantize_mx_rowcol_bf16_ex(uint8_t* qr, uint8_t* scales_r, uint8_t* qc, uin
                                 long long R, int C, long long ldx, long long ldqc, long long tok_off, long long ntok) {
     quantize_mx_rowcol_bf16(qr, scales_r, qc, scales_c, (const bf16_t*)x, R, C, ldx, ldqc, tok_off, ntok, stream());
 }
-void layernorm_backward_stream(uint16_t* dres_out, uint8_t* lo_out, const uint16_t* dres_in, const uint8_t* lo_in,
-                               float* dweight, float* dbias, float* dres_colsum, const uint16_t* dout, const float* inp,
-                               const float* weight, const float* mean, const float* rstd, long long R, int C) {
-    ln_backward_bf16_stream((bf16_t*)dres_out, lo_out, (const bf16_t*)dres_in, lo_in, dweight, dbias, dres_colsum,
-                            (const bf16_t*)dout, inp, weight, mean, rstd, R, C, stream());
-}
 void layernorm_backward_stream_mx(uint16_t* dres_out, uint8_t* lo_out, const uint16_t* dres_in, const uint8_t* lo_in,
                                   float* dweight, float* dbias, float* dres_colsum, const uint16_t* dout,
                                   const float* inp, const float* weight, const float* mean, const float* rstd,
                                   long long R, int C, uint8_t* qr, uint8_t* scales_r, uint8_t* qc, uint8_t* scales_c,
                                   long long ldqc, long long tok_off, long long ntok) {
-    ln_backward_bf16_stream_mx((bf16_t*)dres_out, lo_out, (const bf16_t*)dres_in, lo_in, dweight, dbias, dres_colsum,
-                               (const bf16_t*)dout, inp, weight, mean, rstd, R, C, stream(), nullptr, qr, scales_r, qc,
-                               scales_c, ldqc, tok_off, ntok, nullptr);
+    LnbArgs a;
+    a.dres_out = (bf16_t*)dres_out; a.lo_out = lo_out; a.dres_in = (const bf16_t*)dres_in; a.lo_in = lo_in;
+    a.dw = dweight; a.db = dbias; a.dres_colsum = dres_colsum; a.dout = (const bf16_t*)dout; a.inp = inp;
+    a.w = weight; a.mean = mean; a.rstd = rstd; a.rows = R; a.C = C;
+    a.qr = qr; a.slr = scales_r; a.qc = qc; a.slc = scales_c; a.ldqc = ldqc; a.tok_off = tok_off; a.ntok = ntok;
+    ln_backward_stream(a, stream());
+}
+void layernorm_backward_stream(uint16_t* dres_out, uint8_t* lo_out, const uint16_t* dres_in, const uint8_t* lo_in,
+                               float* dweight, float* dbias, float* dres_colsum, const uint16_t* dout, const float* inp,
+                               const float* weight, const float* mean, const float* rstd, long long R, int C) {
+    layernorm_backward_stream_mx(dres_out, lo_out, dres_in, lo_in, dweight, dbias, dres_colsum, dout, inp, weight, mean,
+                                 rstd, R, C, nullptr, nullptr, nullptr, nullptr, 0, 0, 0);
 }
 void layernorm_forward_mx(uint8_t* qr, uint8_t* scales_r, uint8_t* qc, uint8_t* scales_c, float* mean, float* rstd,
                           const float* inp, const float* weight, const float* bias, long long R, int C, long long ldqc,

@@ -893,32 +893,25 @@ void ln_backward_f32(float* dinp, float* dw, float* db, const float* dout, const
     io.dinp = dinp; io.dweight = dw; io.dbias = db;
     ln_backward_any<float, false>(io, dout, inp, w, mean, rstd, rows, C, s, ws);
 }
-void ln_backward_bf16_stream(bf16_t* dres_out, uint8_t* lo_out, const bf16_t* dres_in, const uint8_t* lo_in,
-                             float* dw, float* db, float* dres_colsum, const bf16_t* dout, const float* inp,
-                             const float* w, const float* mean, const float* rstd, long long rows, int C,
-                             hipStream_t s, float* part) {
-    if (!dres_out || !lo_out || !dres_in || !lo_in) { set_error("layernorm_backward: the bf16 stream needs its 4 planes"); return; }
-    if (((uintptr_t)lo_in | (uintptr_t)lo_out) & 3) { set_error("layernorm_backward: lo8 planes need 4-B alignment"); return; }
-    LnbIo io{};
-    io.hi_out = dres_out; io.lo_out = lo_out; io.hi_in = dres_in; io.lo_in = lo_in;
-    io.dweight = dw; io.dbias = db; io.dsum = dres_colsum; io.part = part;
-    ln_backward_any<bf16_t, true>(io, dout, inp, w, mean, rstd, rows, C, s);
-}
-void ln_backward_bf16_stream_dp(bf16_t* dres_out, uint8_t* lo_out, bf16_t* dres_scaled, const float* row_scale,
-                                const bf16_t* dres_in, const uint8_t* lo_in, float* dw, float* db,
-                                float* dres_colsum, const bf16_t* dout, const float* inp, const float* w,
-                                const float* mean, const float* rstd, long long rows, int C, hipStream_t s,
-                                float* part) {
-    if (!dres_out || !lo_out || !dres_in || !lo_in || !dres_scaled || !row_scale) {
-        set_error("layernorm_backward: the row-scaled bf16 stream needs its 5 planes and the row scales");
-        return;
+bool ln_backward_stream(const LnbArgs& a, hipStream_t s) {
+    const bool dp = a.dres_scaled || a.row_scale;
+    if (a.mx()) {
+        if (dp) { set_error("layernorm_backward_mx: no row-scaled form"); return false; }
+        return ln_backward_stream_mx(a, s);
     }
-    if (((uintptr_t)lo_in | (uintptr_t)lo_out) & 3) { set_error("layernorm_backward: lo8 planes need 4-B alignment"); return; }
+    if (!a.dres_out || !a.lo_out || !a.dres_in || !a.lo_in || (dp && !(a.dres_scaled && a.row_scale))) {
+        set_error(dp ? "layernorm_backward: the row-scaled bf16 stream needs its 5 planes and the row scales"
+                     : "layernorm_backward: the bf16 stream needs its 4 planes");
+        return false;
+    }
+    if (((uintptr_t)a.lo_in | (uintptr_t)a.lo_out) & 3) { set_error("layernorm_backward: lo8 planes need 4-B alignment"); return false; }
     LnbIo io{};
-    io.hi_out = dres_out; io.lo_out = lo_out; io.hi_in = dres_in; io.lo_in = lo_in;
-    io.dweight = dw; io.dbias = db; io.dsum = dres_colsum; io.part = part;
-    io.rscale = row_scale; io.hi_scaled = dres_scaled;
-    ln_backward_any<bf16_t, true, true>(io, dout, inp, w, mean, rstd, rows, C, s);
+    io.hi_out = a.dres_out; io.lo_out = a.lo_out; io.hi_in = a.dres_in; io.lo_in = a.lo_in;
+    io.dweight = a.dw; io.dbias = a.db; io.dsum = a.dres_colsum; io.part = a.part;
+    io.rscale = a.row_scale; io.hi_scaled = a.dres_scaled;
+    if (!dp) ln_backward_any<bf16_t, true>(io, a.dout, a.inp, a.w, a.mean, a.rstd, a.rows, a.C, s);
+    else ln_backward_any<bf16_t, true, true>(io, a.dout, a.inp, a.w, a.mean, a.rstd, a.rows, a.C, s);
+    return true;
 }
 // out[c][r] = in[r][c] for `count` matrices of R x Cc bf16 spaced `stride` elements apart
 // (in and out use the same stride); 64 x 64 tiles through LDS, 16-B global accesses.

@@ -21,20 +21,35 @@ void ln_backward_f32(float* dinp, float* dw, float* db, const float* dout, const
 // GEMM operand, and a byte plane of the rounding residual; lo planes nullable = plain bf16):
 // dres_out = dres_in + LN_dinp(dout); dres_colsum / dw / db as above, taken in fp32 before the
 // rounding; part != null: per-block partial rows [ln_bwd_blocks(rows)][2C or 3C] (dw | db |
-// dres_colsum) instead of atomics, summed later in a fixed order
-void ln_backward_bf16_stream(bf16_t* dres_out, uint8_t* lo_out, const bf16_t* dres_in, const uint8_t* lo_in,
-                             float* dw, float* db, float* dres_colsum, const bf16_t* dout, const float* inp,
-                             const float* w, const float* mean, const float* rstd, long long rows, int C,
-                             hipStream_t s, float* part = nullptr);
-// stochastic depth: the same, with dres_out also the upstream gradient of a residual
-// branch scaled per row in the forward: dres_scaled = bf16(fl32(row_scale[r] * dres_out)) (a bf16 plane
-// of its own, the branch's GEMM operand) and dres_colsum sums those fp32 products; dres_out / lo_out
-// (the pass-through gradient) keep the bits of ln_backward_bf16_stream
-void ln_backward_bf16_stream_dp(bf16_t* dres_out, uint8_t* lo_out, bf16_t* dres_scaled, const float* row_scale,
-                                const bf16_t* dres_in, const uint8_t* lo_in, float* dw, float* db,
-                                float* dres_colsum, const bf16_t* dout, const float* inp, const float* w,
-                                const float* mean, const float* rstd, long long rows, int C, hipStream_t s,
-                                float* part = nullptr);
+// dres_colsum) instead of atomics, summed later in a fixed order (else reduced into dw / db / dres_colsum)
+struct LnbArgs {
+    bf16_t* dres_out = nullptr;
+    uint8_t* lo_out = nullptr;
+    const bf16_t* dres_in = nullptr;
+    const uint8_t* lo_in = nullptr;
+    float *dw = nullptr, *db = nullptr, *dres_colsum = nullptr, *part = nullptr;
+    const bf16_t* dout = nullptr;
+    const float *inp = nullptr, *w = nullptr, *mean = nullptr, *rstd = nullptr;
+    long long rows = 0;
+    int C = 0;
+    // stochastic depth (both or neither): dres_out is also the upstream gradient of a residual
+    // branch scaled per row in the forward: dres_scaled = bf16(fl32(row_scale[r] * dres_out)) (a bf16 plane
+    // of its own, the branch's GEMM operand) and dres_colsum sums those fp32 products; dres_out / lo_out
+    // (the pass-through gradient) keep the bits of the plain form
+    bf16_t* dres_scaled = nullptr;
+    const float* row_scale = nullptr;
+    // fp8 (any of qr / slr / qc / slc set; gemm_fp8.hip, C a multiple of 256 up to 1280: ln_backward_mx_supported):
+    // plus both MX forms of dres_out's bf16 plane, as quantize_mx_rowcol_bf16 writes them.  scratch:
+    // ln_backward_mx_scratch_bytes(C) (nullptr: the thread workspace; a caller with work in flight on other
+    // streams passes its own)
+    uint8_t *qr = nullptr, *slr = nullptr, *qc = nullptr, *slc = nullptr;
+    long long ldqc = 0, tok_off = 0, ntok = 0;
+    uint8_t* scratch = nullptr;
+    bool mx() const { return qr || slr || qc || slc; }
+};
+// the plain, row-scaled or MX kernel by which optional parts are set (false + set_error on a bad call)
+bool ln_backward_stream(const LnbArgs& a, hipStream_t s);
+bool ln_backward_stream_mx(const LnbArgs& a, hipStream_t s);  // gemm_fp8.hip: the MX form's kernel, for the launcher
 int ln_bwd_blocks(long long rows);
 void convert_f2bf(bf16_t* out, const float* inp, long long n, hipStream_t s);
 // e = ema_blend(e, p) over n elements on s (the body of ema_update, include/vit_ops.h; common.h ema_blend)

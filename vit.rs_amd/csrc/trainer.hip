@@ -402,7 +402,6 @@ struct Trainer {
     float* red_ws = nullptr;
     float* sg_part[2]{};
     long long sg_ln2 = 0, sg_ln1 = 0, sg_fcb = 0, sg_qkv = 0;  // offsets (floats) in sg_part[p]
-    int fcb_rows = 0;  // fc-bias column-sum partial rows per micro-batch (gemm_colsum_rows of the fcproj dgrad)
     bf16_t* dln_bf = nullptr;  // bf16 mode: LN-output gradient from the fc / qkv dgrad GEMMs
     bf16_t *dres_bf = nullptr, *dres_bf2 = nullptr, *dfch = nullptr, *datty = nullptr, *dqkv = nullptr, *dpatch_bf = nullptr;
     float* dpatch_f = nullptr;
@@ -449,14 +448,26 @@ struct Trainer {
     bool layered(int ti) const { return ti >= P_LN1W && ti <= P_FCPROJB; }
     bool lowp() const { return prec != VIT_FP32; }  // bf16 or fp8 mode (the fast path)
     bool fp8() const { return prec == VIT_FP8; }
+    // the four layer-weight kinds (every mode): tensor index and the forward view N x K of one layer
+    static constexpr int NWK = 4;
+    struct WKind { int ti; long long N, K; };
+    WKind wkind(int k) const {
+        const WKind t[NWK] = {{P_QKVW, 3LL * C, C}, {P_ATTPROJW, C, C}, {P_FCW, 4LL * C, C}, {P_FCPROJW, C, 4LL * C}};
+        return t[k];
+    }
+    // the L layers of kind k lie a constant stride apart in the arenas, in reverse layer order: the
+    // lowest-addressed layer l0 (what a batched launch over all layers is given) and the stride's magnitude
+    struct WSpan { int l0; long long stride; };
+    WSpan wspan(int k) const {
+        const int ti = wkind(k).ti;
+        const long long st = L > 1 ? off[ti * L + 1] - off[ti * L] : 0;
+        return {st < 0 ? L - 1 : 0, st < 0 ? -st : st};
+    }
     // ---- fp8 mode: MXFP8 copies of the four layer weights (forward B operand, [N][K]) and of their
     // transposes (input-gradient B operand, [Cin][OC]), refreshed after every optimizer step, and
     // per-micro-batch scratch for the quantized A operand of each fp8 GEMM
-    static constexpr int NWK = 4;
-    const int wkinds[NWK] = {P_QKVW, P_ATTPROJW, P_FCW, P_FCPROJW};
     struct QMat { uint8_t* q = nullptr; uint8_t* s = nullptr; };
     QMat wq[NWK], wtq[NWK];            // [L] matrices each, in the source's memory order
-    long long wq_n[NWK]{}, wq_k[NWK]{};  // forward view: N x K per layer
     uint8_t* act_q[4]{};
     uint8_t* act_s[4]{};
     // fused MX outputs (fp8 mode): the GELU output of fc fwd / the GELU' output of fcproj dgrad,
@@ -489,7 +500,7 @@ struct Trainer {
     // at ViT-H/14 (the other micro-batch stream already fills the partial round)
     bool lnmx_on() const { return rowcol_on() && ln_forward_mx_supported(C); }
     // fp8: the residual-gradient LayerNorm backwards also write both MX forms of dres2 / dres3
-    // (ln_backward_bf16_stream_mx; else the rowcol quantize)
+    // (ln_backward_stream's MX form; else the rowcol quantize)
     uint8_t* lnb_scr[4]{};  // per micro-batch stream: the LayerNorm backward -> MX kernel's scratch
     bool lnbmx_on() const { return rowcol_on() && ln_backward_mx_supported(C); }
     // the column-form span of micro-batch mb (R rows): the last one carries the padding tokens
@@ -500,12 +511,9 @@ struct Trainer {
     QMat actc_of(int k, int l) const {
         return {actc[k].q + (long long)l * C * kp_tok, actc[k].s + (long long)l * mx_scale_bytes(C, (int)kp_tok)};
     }
-    int wslot(int k, int l) const {    // memory-order index of layer l's copy of weight kind k
-        const long long stride = L > 1 ? off[wkinds[k] * L + 1] - off[wkinds[k] * L] : 0;
-        return stride < 0 ? L - 1 - l : l;
-    }
+    int wslot(int k, int l) const { return std::abs(l - wspan(k).l0); }  // memory-order index of layer l's copy of kind k
     int wkind_of(int ti) const {
-        for (int k = 0; k < NWK; k++) if (wkinds[k] == ti) return k;
+        for (int k = 0; k < NWK; k++) if (wkind(k).ti == ti) return k;
         return -1;
     }
     long long per_layer(int ti) const { return canon_size[ti] / L; }
@@ -598,17 +606,19 @@ struct Trainer {
         if (bf) gemm_bf16(a, st); else gemm_f32(a, st);
         tend();
     }
-    // fork the micro-batch streams off s / join them back into s
+    // cross-stream ordering: what is enqueued on `to` from here on runs after everything enqueued on `from` so far
+    void order(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+        VIT_HIP(hipEventRecord(ev, from));
+        VIT_HIP(hipStreamWaitEvent(to, ev, 0));
+    }
+    // fork the micro-batch streams off s (one record, a wait on each) / join them back into s
     void mb_fork() {
         if (nmb < 2) return;
         VIT_HIP(hipEventRecord(fork_ev, s));
         for (int k = 1; k < nmb; k++) VIT_HIP(hipStreamWaitEvent(ms[k], fork_ev, 0));
     }
     void mb_join() {
-        for (int k = 1; k < nmb; k++) {
-            VIT_HIP(hipEventRecord(join_ev[k], ms[k]));
-            VIT_HIP(hipStreamWaitEvent(s, join_ev[k], 0));
-        }
+        for (int k = 1; k < nmb; k++) order(join_ev[k], ms[k], s);
     }
 
     // ------------------------------------------------------------------------------
@@ -773,14 +783,12 @@ struct Trainer {
                 sg_part[1] = alloc<float>(n);
             }
             if (fp8()) {
-                const long long ns[NWK] = {3LL * C, C, 4LL * C, C}, ks[NWK] = {C, C, C, 4LL * C};
                 for (int k = 0; k < NWK; k++) {
-                    wq_n[k] = ns[k];
-                    wq_k[k] = ks[k];
-                    wq[k].q = alloc<uint8_t>(L * ns[k] * ks[k]);
-                    wq[k].s = alloc<uint8_t>((long long)L * mx_scale_bytes(ns[k], (int)ks[k]));
-                    wtq[k].q = alloc<uint8_t>(L * ns[k] * ks[k]);
-                    wtq[k].s = alloc<uint8_t>((long long)L * mx_scale_bytes(ks[k], (int)ns[k]));
+                    const WKind w = wkind(k);
+                    wq[k].q = alloc<uint8_t>(L * w.N * w.K);
+                    wq[k].s = alloc<uint8_t>((long long)L * mx_scale_bytes(w.N, (int)w.K));
+                    wtq[k].q = alloc<uint8_t>(L * w.N * w.K);
+                    wtq[k].s = alloc<uint8_t>((long long)L * mx_scale_bytes(w.K, (int)w.N));
                 }
                 // A-operand scratch per micro-batch stream: rows x (widest K = 4C) bytes + scales.
                 // Stream k runs only when there are > k micro-batches, so it holds at most
@@ -905,8 +913,7 @@ struct Trainer {
     // which s waits for before the backward's first gradient write (backward_bf16)
     bool pre_side_on() const { return two_streams && lowp() && !timing && s2; }
     hipStream_t pre_side_begin() {
-        VIT_HIP(hipEventRecord(bev[EV_PRE_IN], s));
-        VIT_HIP(hipStreamWaitEvent(s2, bev[EV_PRE_IN], 0));
+        order(bev[EV_PRE_IN], s, s2);
         return s2;
     }
     void pre_side_end() {
@@ -929,8 +936,6 @@ struct Trainer {
     // pbfT <- transposes of the layer weights in pbf (after every SGD step): one launch per
     // weight kind over all L layers (the layers of a kind are a constant stride apart)
     void refresh_transposed() {
-        const int kinds[4] = {P_QKVW, P_ATTPROJW, P_FCW, P_FCPROJW};
-        const int rows[4] = {3 * C, C, 4 * C, C}, cols[4] = {C, C, C, 4 * C};
         tbeg(TC_MISC, 0);
         // bf16 mode: only the backward's dgrads read the transposes, so with side pre-work on they run
         // on s2 beside the next forward (s waits for them at the start of the backward).  fp8 mode
@@ -938,11 +943,10 @@ struct Trainer {
         const bool side = pre_side_on() && !fp8();
         hipStream_t ts = side ? pre_side_begin() : s;
         // fp8 mode reads no bf16 transposed copy (refresh_fp8 column-quantizes W for the dgrads)
-        for (int k = 0; k < 4 && !(fp8() && wt_cols); k++) {
-            const long long stride = L > 1 ? off[kinds[k] * L + 1] - off[kinds[k] * L] : 0;
-            // negative stride: pass the lowest-addressed layer (layers are stored in reverse)
-            const int l0 = stride < 0 ? L - 1 : 0;
-            transpose_bf16(WT(kinds[k], l0), W(kinds[k], l0), rows[k], cols[k], L, stride < 0 ? -stride : stride, ts);
+        for (int k = 0; k < NWK && !(fp8() && wt_cols); k++) {
+            const WKind w = wkind(k);
+            const WSpan sp = wspan(k);
+            transpose_bf16(WT(w.ti, sp.l0), W(w.ti, sp.l0), (int)w.N, (int)w.K, L, sp.stride, ts);
         }
         if (side) pre_side_end();
         if (patch_pad)  // the patch weight's padded copy (columns KP .. KPP-1 stay zero)
@@ -956,28 +960,28 @@ struct Trainer {
     void refresh_fp8() {
         tbeg(TC_QUANT, 0);
         for (int k = 0; k < NWK; k++) {
-            const long long stride = L > 1 ? off[wkinds[k] * L + 1] - off[wkinds[k] * L] : 0;
-            const int l0 = stride < 0 ? L - 1 : 0;
-            const long long as = stride < 0 ? -stride : stride;
-            const long long N = wq_n[k], K = wq_k[k];
-            quantize_mx_batched_f32(wq[k].q, wq[k].s, P(wkinds[k], l0), N, (int)K, L, as, N * K,
+            const int ti = wkind(k).ti, l0 = wspan(k).l0;
+            const long long N = wkind(k).N, K = wkind(k).K, as = wspan(k).stride;
+            quantize_mx_batched_f32(wq[k].q, wq[k].s, P(ti, l0), N, (int)K, L, as, N * K,
                                     (long long)mx_scale_bytes(N, (int)K), s);
             if (wt_cols)  // Wt's MX rows = W's MX columns: byte-identical, without the bf16 transpose
-                quantize_mx_cols_batched_bf16(wtq[k].q, wtq[k].s, W(wkinds[k], l0), N, (int)K, K, L, as, N * K,
+                quantize_mx_cols_batched_bf16(wtq[k].q, wtq[k].s, W(ti, l0), N, (int)K, K, L, as, N * K,
                                               (long long)mx_scale_bytes(K, (int)N), s);
             else
-                quantize_mx_batched_bf16(wtq[k].q, wtq[k].s, WT(wkinds[k], l0), K, (int)N, L, as, N * K,
+                quantize_mx_batched_bf16(wtq[k].q, wtq[k].s, WT(ti, l0), K, (int)N, L, as, N * K,
                                          (long long)mx_scale_bytes(K, (int)N), s);
         }
         tend();
     }
     QMat wq_of(int ti, int l) const {
         const int k = wkind_of(ti), j = wslot(k, l);
-        return {wq[k].q + (long long)j * wq_n[k] * wq_k[k], wq[k].s + (long long)j * mx_scale_bytes(wq_n[k], (int)wq_k[k])};
+        const WKind w = wkind(k);
+        return {wq[k].q + (long long)j * w.N * w.K, wq[k].s + (long long)j * mx_scale_bytes(w.N, (int)w.K)};
     }
     QMat wtq_of(int ti, int l) const {
         const int k = wkind_of(ti), j = wslot(k, l);
-        return {wtq[k].q + (long long)j * wq_n[k] * wq_k[k], wtq[k].s + (long long)j * mx_scale_bytes(wq_k[k], (int)wq_n[k])};
+        const WKind w = wkind(k);
+        return {wtq[k].q + (long long)j * w.N * w.K, wtq[k].s + (long long)j * mx_scale_bytes(w.K, (int)w.N)};
     }
     // a forward (transposed = false) or input-gradient (true) GEMM of weight ti, layer l: bf16
     // mode as given; fp8 mode quantizes the bf16 A operand into the stream's scratch and runs the
@@ -1053,27 +1057,31 @@ struct Trainer {
         w.k_period = k_period;  // (bf16 engine: dout's rows off k_period are exact zeros, last_cls_bwd)
         return w;
     }
-    // layer l's fcproj dgrad of micro-batch mb into d1: full size (false), or (last_cls_bwd = 2, last block)
-    // gathered on the CLS rows when T >= 128, the full-size call would run on the 256x256 engine (not the
-    // ping-pong engine, whose partial rows are 96 tall) and the fc
-    // weight gradient of the step skips the K-steps without a CLS row (it then reads dfch in the CLS rows'
-    // 32-row blocks only).  Sets fcb_rows (the full-size call's partial rows per micro-batch).
-    bool lc_d1_gathered(int l, int mb, const bf16_t* dres3, GemmArgs& d1) {
-        const int Bm = B / nmb;
-        const long long R = (long long)Bm * T, r0 = mb * R;
-        LayerActs& a = la[l];
-        d1 = GemmArgs();
+    // layer l's fcproj input gradient of micro-batch mb, full size: dfch = (dres3 . fcprojw) * gelu'(fch) (stored
+    // as fchd), its column sums (fc_b) into the micro-batch's partial rows
+    GemmArgs d1_args(int l, int mb, const bf16_t* dres3) const {
+        const long long R = (long long)(B / nmb) * T, r0 = mb * R;
+        GemmArgs d1;
         d1.A = dres3 + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C);
-        d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
+        d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = la[l].fchd + r0 * 4 * C; d1.ldaux = 4 * C;
         d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
-        fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
-        d1.colsum_part = sg_rows(l, sg_fcb) + (long long)mb * fcb_rows * 4 * C;
-        if (!(last_cls_on() && lc_bwd >= 2 && l == L - 1 && T >= 128 && R >= 256)) return false;
+        d1.colsum_part = sg_rows(l, sg_fcb) + (long long)mb * gemm_colsum_rows(d1, fp8()) * 4 * C;
+        return d1;
+    }
+    // fc-bias column-sum partial rows per micro-batch: those of the full-size fcproj dgrad (engine-dependent; the
+    // call has the same shape in every layer and micro-batch)
+    int fcb_rows() const { return gemm_colsum_rows(d1_args(0, 0, dres_bf), fp8()); }
+    // last_cls_bwd = 2: the last block's d1_args gathered on the CLS rows, when T >= 128, the full-size call
+    // would run on the 256x256 engine (not the ping-pong engine, whose partial rows are 96 tall) and the fc
+    // weight gradient of the step skips the K-steps without a CLS row (it then reads dfch in the CLS rows'
+    // 32-row blocks only).  false: d1 stays full size
+    bool d1_gather(GemmArgs& d1) const {
+        if (!(last_cls_on() && lc_bwd >= 2 && T >= 128 && d1.M >= 256)) return false;
         GemmArgs g = d1;
-        g.M = Bm; g.lda = (long long)T * C; g.ldc = (long long)T * 4 * C; g.ldaux = (long long)T * 4 * C;
+        g.M = B / nmb; g.lda = (long long)T * C; g.ldc = (long long)T * 4 * C; g.ldaux = (long long)T * 4 * C;
         g.rows_gathered = true; g.colsum_row_period = T;
-        if (!gemm_colsum_period_ok(g) || gemm_colsum_rows(g, false) != fcb_rows) return false;
-        if (!gemm_bf16_kskip(wgrad_args(dfch, 4 * C, a.ln2, C, G(P_FCW, l), T))) return false;
+        if (!gemm_colsum_period_ok(g) || gemm_colsum_rows(g, false) != fcb_rows()) return false;
+        if (!gemm_bf16_kskip(wgrad_args(dfch, 4 * C, la[L - 1].ln2, C, G(P_FCW, L - 1), T))) return false;
         d1 = g;
         return true;
     }
@@ -1088,8 +1096,7 @@ struct Trainer {
         if (!lc_dirty) return;
         hipStream_t cs = s;
         if (two_streams && s2) {
-            VIT_HIP(hipEventRecord(bev[EV_LC_IN], s));
-            VIT_HIP(hipStreamWaitEvent(s2, bev[EV_LC_IN], 0));
+            order(bev[EV_LC_IN], s, s2);
             cs = s2;
         }
         VIT_HIP(hipMemsetAsync(dln_bf, 0, (size_t)BT * C * 2, cs));
@@ -1098,10 +1105,10 @@ struct Trainer {
         // partial rows.  The fc weight gradient reads dfch in the CLS rows' 32-row blocks, which hold layer
         // 0's rows (nothing else reads a non-CLS row of dfch in the last block), and the fixed-order reduce
         // reads every partial row
-        GemmArgs d1;
-        lc_d1_clean = lc_d1_gathered(L - 1, 0, dres_bf, d1);
+        GemmArgs d1 = d1_args(L - 1, 0, dres_bf);
+        lc_d1_clean = d1_gather(d1);
         if (lc_d1_clean) {
-            VIT_HIP(hipMemsetAsync(sg_rows(L - 1, sg_fcb), 0, (size_t)nmb * fcb_rows * 4 * C * sizeof(float), cs));
+            VIT_HIP(hipMemsetAsync(sg_rows(L - 1, sg_fcb), 0, (size_t)nmb * fcb_rows() * 4 * C * sizeof(float), cs));
             clear_cls_blocks_k<<<dim3(8, B), 256, 0, cs>>>(dfch, T, BT, 4 * C);
         }
         if (cs != s) {
@@ -1194,34 +1201,59 @@ struct Trainer {
     }
 
     // ------------------------------------------------------------------ bf16 fast path
+    // patch embedding (encoder_forward, train_vit.rs:196 -> ViT), each micro-batch on its stream.  The im2col rows
+    // and the weight's rows are KPP wide: KP, or padded (patch_pad: zero-padded rows, the padded weight copy)
+    void patch_forward() {
+        const int Bm = B / nmb;
+        for (int mb = 0; mb < nmb; mb++) {
+            hipStream_t st = ms[mb];
+            const long long img0 = (long long)mb * Bm;
+            bf16_t* pt = patches_bf + img0 * NP * KPP;
+            const float* px = pixels + img0 * 3 * cfg.img * cfg.img;
+            tbeg(TC_PATCH, 2.0 * Bm * NP * (double)KP * C, st);
+            if (patch_pad) im2col_pad_bf16(pt, px, Bm, cfg.img, cfg.patch, KPP, st);
+            else im2col_bf16(pt, px, Bm, cfg.img, cfg.patch, st);
+            GemmArgs a;
+            a.A = pt; a.lda = KPP; a.B = patch_pad ? wpatch_pad : W(P_PATCH_W); a.ldb = KPP;
+            a.C = emb_tmp + img0 * NP * C; a.ldc = C; a.bias = P(P_PATCH_B);
+            a.M = Bm * NP; a.N = C; a.K = KPP; a.epi = EPI_F32_STORE;
+            gemm_bf16(a, st);
+            patch_assemble(encoded + img0 * T * C, emb_tmp + img0 * NP * C, P(P_CLS), P(P_WPE), Bm, NP, C, st);
+            tend();
+        }
+    }
+    // LayerNorm 1 (second = false: of the block's input) or 2 (of res2) of layer l: what its forward and its
+    // backward share.  Pointers at row 0; colk: the index of its output's column form in actc
+    struct LnSite { bf16_t* out; float *mean, *rstd; const float* inp; int tw, tb, colk; };
+    LnSite ln_site(int l, bool second) const {
+        const LayerActs& a = la[l];
+        if (second) return {a.ln2, a.ln2_mean, a.ln2_rstd, a.res2, P_LN2W, P_LN2B, 2};
+        return {a.ln1, a.ln1_mean, a.ln1_rstd, l == 0 ? encoded : la[l - 1].res3, P_LN1W, P_LN1B, 0};
+    }
+    // its forward on micro-batch mb: `rows` rows at row stride rs (last_cls: the CLS rows, in place), into bf16, or
+    // (lnmx_on(): whole micro-batches only) into its two MX forms alone: the next GEMM's A operand in act_q and
+    // the column form its weight gradient reads
+    void ln_fwd(int l, int mb, bool second, long long rows, long long rs) {
+        const LnSite n = ln_site(l, second);
+        hipStream_t st = ms[mb];
+        const long long r0 = (long long)mb * (B / nmb) * T;
+        tbeg(TC_LN_FWD, 0, st);
+        if (lnmx_on()) {
+            const QMat c = actc_of(n.colk, l);
+            ln_forward_mx(act_q[mb], act_s[mb], c.q, c.s, n.mean + r0, n.rstd + r0, n.inp + r0 * C, P(n.tw, l), P(n.tb, l),
+                          rows, C, kp_tok, r0, mb_ntok(mb, rows), st, nullptr);
+        } else {
+            ln_forward_bf16(n.out + r0 * C, n.mean + r0, n.rstd + r0, n.inp + r0 * C, P(n.tw, l), P(n.tb, l), rows, C, st, rs);
+        }
+        tend();
+    }
     void forward_bf16() {
         const int Bm = B / nmb;
         const long long R = (long long)Bm * T;  // rows per micro-batch
         lc_active = last_cls_on();
         if (lc_active) last_cls_clear();
         mb_fork();
-        for (int mb = 0; mb < nmb; mb++) {
-            // patch embedding (encoder_forward, train_vit.rs:196 -> ViT)
-            hipStream_t st = ms[mb];
-            const long long img0 = (long long)mb * Bm;
-            tbeg(TC_PATCH, 2.0 * Bm * NP * (double)KP * C, st);
-            GemmArgs a;
-            a.C = emb_tmp + img0 * NP * C; a.ldc = C; a.bias = P(P_PATCH_B);
-            a.M = Bm * NP; a.N = C; a.K = KP; a.epi = EPI_F32_STORE;
-            if (patch_pad) {
-                im2col_pad_bf16(patches_bf + img0 * NP * KPP, pixels + img0 * 3 * cfg.img * cfg.img, Bm, cfg.img,
-                                cfg.patch, KPP, st);
-                a.A = patches_bf + img0 * NP * KPP; a.lda = KPP; a.B = wpatch_pad; a.ldb = KPP; a.K = KPP;
-                gemm_bf16(a, st);
-            } else {
-                im2col_bf16(patches_bf + img0 * NP * KP, pixels + img0 * 3 * cfg.img * cfg.img, Bm, cfg.img,
-                            cfg.patch, st);
-                a.A = patches_bf + img0 * NP * KP; a.lda = KP; a.B = W(P_PATCH_W); a.ldb = KP;
-                gemm_bf16(a, st);
-            }
-            patch_assemble(encoded + img0 * T * C, emb_tmp + img0 * NP * C, P(P_CLS), P(P_WPE), Bm, NP, C, st);
-            tend();
-        }
+        patch_forward();
         for (int l = 0; l < L; l++) {
             LayerActs& a = la[l];
             const float* xl = l == 0 ? encoded : la[l - 1].res3;
@@ -1239,13 +1271,7 @@ struct Trainer {
                 const bool rc = rowcol_on(), lm = lnmx_on();
                 QMat c_ln1 = rc ? actc_of(0, l) : QMat{}, c_atty = rc ? actc_of(1, l) : QMat{},
                      c_ln2 = rc ? actc_of(2, l) : QMat{};
-                tbeg(TC_LN_FWD, 0, st);
-                if (lm)  // ln1 only in its two MX forms (the qkv GEMM's A operand, the qkv wgrad's B)
-                    ln_forward_mx(act_q[mb], act_s[mb], c_ln1.q, c_ln1.s, a.ln1_mean + r0, a.ln1_rstd + r0, x,
-                                  P(P_LN1W, l), P(P_LN1B, l), R, C, kp_tok, r0, mb_ntok(mb, R), st, nullptr);
-                else
-                    ln_forward_bf16(a.ln1 + r0 * C, a.ln1_mean + r0, a.ln1_rstd + r0, x, P(P_LN1W, l), P(P_LN1B, l), R, C, st);
-                tend();
+                ln_fwd(l, mb, false, R, 1);
                 GemmArgs q;
                 q.A = a.ln1 + r0 * C; q.lda = C; q.B = W(P_QKVW, l); q.ldb = C; q.C = a.qkv + r0 * 3 * C;
                 q.ldc = 3 * C; q.bias = P(P_QKVB, l); q.M = (int)R; q.N = 3 * C; q.K = C; q.epi = EPI_BF16_STORE;
@@ -1262,14 +1288,7 @@ struct Trainer {
                     pr.epi = EPI_F32_RESID_RS; pr.row_scale = dp_scale(l, 0, r0); pr.ld_row_scale = rs;
                 }
                 gemm_w(TC_PROJ_FWD, pr, P_ATTPROJW, l, false, mb, st, PRE_NONE, false, rc ? &c_atty : nullptr);
-                tbeg(TC_LN_FWD, 0, st);
-                if (lm)
-                    ln_forward_mx(act_q[mb], act_s[mb], c_ln2.q, c_ln2.s, a.ln2_mean + r0, a.ln2_rstd + r0,
-                                  a.res2 + r0 * C, P(P_LN2W, l), P(P_LN2B, l), R, C, kp_tok, r0, mb_ntok(mb, R), st, nullptr);
-                else
-                    ln_forward_bf16(a.ln2 + r0 * C, a.ln2_mean + r0, a.ln2_rstd + r0, a.res2 + r0 * C, P(P_LN2W, l),
-                                    P(P_LN2B, l), Mr, C, st, rs);
-                tend();
+                ln_fwd(l, mb, true, Mr, rs);
                 GemmArgs f;
                 // fc: fchg = gelu(pre) for fcproj, fchd = gelu'(pre) for the fcproj dgrad (one sigmoid)
                 f.A = a.ln2 + r0 * C; f.lda = rs * C; f.B = W(P_FCW, l); f.ldb = C; f.C = a.fchd + r0 * 4 * C;
@@ -1306,8 +1325,8 @@ struct Trainer {
         hipStream_t st = two_streams ? s2 : s;
         if (two_streams) {
             for (int mb = 0; mb < nmb; mb++) {
-                if (!dout_c) VIT_HIP(hipEventRecord(mev[mb][ready], ms[mb]));
-                VIT_HIP(hipStreamWaitEvent(s2, mev[mb][ready], 0));
+                if (dout_c) VIT_HIP(hipStreamWaitEvent(s2, mev[mb][ready], 0));
+                else order(mev[mb][ready], ms[mb], s2);
             }
         }
         if (fp8()) {
@@ -1337,19 +1356,14 @@ struct Trainer {
         if (two_streams) VIT_HIP(hipStreamWaitEvent(st, bev[done], 0));
     }
 
-    float* sg_rows(int l, long long off) { return sg_part[l & 1] + off; }
+    float* sg_rows(int l, long long off) const { return sg_part[l & 1] + off; }
     // the layer's small gradients from the micro-batches' partial rows, in a fixed order, on the
     // weight-gradient stream once every micro-batch stream has finished the layer (LN1 backward).
     // Layer l-2 reuses this parity's rows only after waits on wgrad events recorded after this
     // reduce (after_wgrad in layer l-1 / l-2), so one pair of buffers suffices.
     void sg_finalize(int l, long long R) {
         hipStream_t st = two_streams ? s2 : s;
-        if (two_streams) {
-            for (int mb = 0; mb < nmb; mb++) {
-                VIT_HIP(hipEventRecord(mev[mb][EV_SG], ms[mb]));
-                VIT_HIP(hipStreamWaitEvent(s2, mev[mb][EV_SG], 0));
-            }
-        }
+        for (int mb = 0; mb < nmb && two_streams; mb++) order(mev[mb][EV_SG], ms[mb], s2);
         const int nb = nmb * ln_bwd_blocks(R), w1 = l > 0 ? 3 * C : 2 * C;
         const float* p2 = sg_rows(l, sg_ln2);
         const float* p1 = sg_rows(l, sg_ln1);
@@ -1359,7 +1373,7 @@ struct Trainer {
             {G(P_ATTPROJB, l), p2 + 2 * C, nb, 3 * C, C},
             {G(P_LN1W, l), p1, nb, w1, C},
             {G(P_LN1B, l), p1 + C, nb, w1, C},
-            {G(P_FCB, l), sg_rows(l, sg_fcb), nmb * fcb_rows, 4 * C, 4 * C},
+            {G(P_FCB, l), sg_rows(l, sg_fcb), nmb * fcb_rows(), 4 * C, 4 * C},
             {G(P_QKVB, l), sg_rows(l, sg_qkv), nmb, 3 * C, 3 * C},
             {l > 0 ? G(P_FCPROJB, l - 1) : nullptr, p1 + 2 * C, nb, w1, C},
         };
@@ -1368,6 +1382,40 @@ struct Trainer {
         tend();
     }
 
+    // LayerNorm backward of the residual-gradient stream on micro-batch mb (R rows) of layer l:
+    //   LN2 (second): dres2 = dres3 + LN2'(dln2) into dres_bf2 / dres_lo2; attproj_b += colsum(dres2)
+    //   LN1:          dres  = dres2 + LN1'(dln1) into dres_bf / dres_lo;   fcproj_b of layer l-1 += colsum(dres)
+    // dw | db | that bias go to the micro-batch's partial rows (sg_finalize).  Where a residual branch reads the
+    // output (LN2, and LN1 above layer 0), also what that branch's GEMMs take in its place: with stochastic
+    // depth the plane scaled by the branch's rows (the bias from the products), in fp8 mode (lnbmx_on()) its two
+    // MX forms, the dgrad's A operand in act_q and the wgrad's dout in dcol, whose weight gradient waits for
+    // the EV_RESB / EV_RESA recorded here
+    void ln_bwd(int l, int mb, bool second, long long R) {
+        const LnSite n = ln_site(l, second);
+        const long long r0 = mb * R;
+        const bool branch = second || l > 0;
+        LnbArgs a;
+        a.dres_out = (second ? dres_bf2 : dres_bf) + r0 * C; a.lo_out = (second ? dres_lo2 : dres_lo) + r0 * C;
+        a.dres_in = (second ? dres_bf : dres_bf2) + r0 * C; a.lo_in = (second ? dres_lo : dres_lo2) + r0 * C;
+        a.dw = G(n.tw, l); a.db = G(n.tb, l);
+        a.dres_colsum = second ? G(P_ATTPROJB, l) : l > 0 ? G(P_FCPROJB, l - 1) : nullptr;
+        a.dout = dln_bf + r0 * C; a.inp = n.inp + r0 * C; a.w = P(n.tw, l); a.mean = n.mean + r0; a.rstd = n.rstd + r0;
+        a.rows = R; a.C = C;
+        a.part = sg_rows(l, second ? sg_ln2 : sg_ln1) + (long long)mb * ln_bwd_blocks(R) * (a.dres_colsum ? 3 : 2) * C;
+        const bool mx = branch && lnbmx_on();
+        if (mx) {
+            const QMat& c = dcol[second ? 1 : 0];
+            a.qr = act_q[mb]; a.slr = act_s[mb]; a.qc = c.q; a.slc = c.s;
+            a.ldqc = kp_tok; a.tok_off = r0; a.ntok = mb_ntok(mb, R); a.scratch = lnb_scr[mb];
+        } else if (branch && dp_bwd) {
+            a.dres_scaled = (second ? dres_s2 : dres_s) + r0 * C;
+            a.row_scale = second ? dp_scale(l, 0, r0) : dp_scale(l - 1, 1, r0);
+        }
+        tbeg(TC_LN_BWD, 0, ms[mb]);
+        ln_backward_stream(a, ms[mb]);
+        if (mx && two_streams) VIT_HIP(hipEventRecord(mev[mb][second ? EV_RESB : EV_RESA], ms[mb]));
+        tend();
+    }
     void backward_bf16() {
         pre_side_wait();  // the arena clear and the transposed weights (side pre-work on s2)
         last_cls_wait();  // the per-step clears of dln_bf / datty (the micro-batch streams fork off s below)
@@ -1380,9 +1428,7 @@ struct Trainer {
         // and writes the other (its column sum, the next bias gradient, is taken in fp32)
         bf16_t* rbA = dres_bf;   // dres3 (read by the fcproj dgrad / wgrad and LN2 backward)
         bf16_t* rbB = dres_bf2;  // dres2 (read by the attproj dgrad / wgrad and LN1 backward)
-        uint8_t* loA = dres_lo;
-        uint8_t* loB = dres_lo2;
-        head_backward(nullptr, rbA, loA);
+        head_backward(nullptr, rbA, dres_lo);
         chunk_done(0);
         // bias gradients are fused into the kernels that produce each gradient tensor:
         //   fcproj_b += colsum(dres3): LN1-backward of layer l+1 (head rows for the last layer)
@@ -1412,7 +1458,6 @@ struct Trainer {
         const long long R = (long long)Bm * T;
         for (int l = L - 1; l >= 0; l--) {
             LayerActs& a = la[l];
-            const float* xl = l == 0 ? encoded : la[l - 1].res3;
             // last_cls: dres3 is zero off the CLS rows (head_backward), so dfch, dln2 and dres2 are too: the
             // fc and attproj input gradients run on the Bm CLS rows (row stride T, in place), and the rows
             // they skip were cleared (last_cls_clear).  The weight gradients, the fcproj dgrad and LayerNorm 2
@@ -1425,31 +1470,36 @@ struct Trainer {
             // last_cls_bwd: the three weight gradients' dout (dres3, dfch, dres2) is exact zeros off the CLS
             // rows, so their split-K engine walks only the K-steps that hold a CLS row (GemmArgs::k_period)
             const int kper = lc && lc_bwd >= 1 ? T : 0;
-            // rowcol: the weight gradients whose dout column form the dgrads' quantize step writes
-            // are issued after those dgrads (s2 waits on the event recorded after the quantize)
-            const bool rc = rowcol_on();
-            QMat c_ln1 = rc ? actc_of(0, l) : QMat{}, c_atty = rc ? actc_of(1, l) : QMat{}, c_ln2 = rc ? actc_of(2, l) : QMat{};
+            // rowcol: the weight gradients whose dout column form the dgrads' quantize step (or the LayerNorm
+            // backward) writes are issued behind those dgrads (s2 waits on the event recorded after the
+            // quantize), every other one ahead of them.  Each is described once; in fp8 mode sA / sB are rbA / rbB
+            // and kper is 0
+            const bool rc = rowcol_on(), ec = epicol_on();
+            const QMat c_ln1 = rc ? actc_of(0, l) : QMat{}, c_atty = rc ? actc_of(1, l) : QMat{},
+                       c_ln2 = rc ? actc_of(2, l) : QMat{}, c_fchg = ec ? fchgc_of(l) : QMat{};
+            auto w_fcproj = [&] {  // fcprojw += dres3^T . fchg
+                wgrad(TC_FCPROJ_WGRAD, sA, C, a.fchg, 4 * C, G(P_FCPROJW, l), EV_RESA, EV_W1, rc ? &dcol[0] : nullptr,
+                      ec ? &c_fchg : nullptr, kper);
+            };
+            auto w_attproj = [&] {  // attprojw += dres2^T . atty
+                wgrad(TC_PROJ_WGRAD, sB, C, a.atty, C, G(P_ATTPROJW, l), EV_RESB, EV_W3, rc ? &dcol[1] : nullptr,
+                      rc ? &c_atty : nullptr, kper);
+            };
+            auto w_qkv = [&] {  // qkvw += dqkv^T . ln1
+                wgrad(TC_QKV_WGRAD, dqkv, 3 * C, a.ln1, C, G(P_QKVW, l), EV_DQKV, EV_W4, rc ? &dcol[2] : nullptr,
+                      rc ? &c_ln1 : nullptr);
+            };
             // lbm: the LayerNorm backwards write dres2 / dres3's MX forms (dres3 of the last layer comes
             // from the head and is quantized by the fcproj dgrad as before)
             const bool lbm = lnbmx_on(), resa_pre = lbm && l < L - 1;
-            // fcproj: dfch = (dres3 . fcprojw) * gelu'(fch) (stored as fchd);  fcprojw += dres3^T . fchg
-            const bool ec = epicol_on();
-            QMat c_fchg = ec ? fchgc_of(l) : QMat{};
-            if (!rc) wgrad(TC_FCPROJ_WGRAD, sA, C, a.fchg, 4 * C, G(P_FCPROJW, l), EV_RESA, EV_W1, nullptr, nullptr, kper);
+            // fcproj: dfch = (dres3 . fcprojw) * gelu'(fch) (stored as fchd)
+            if (!rc) w_fcproj();
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 after_wgrad(EV_W2, ms[mb]);  // the previous layer's fc wgrad has read dfch
-                GemmArgs d1, d1g;
+                GemmArgs d1 = d1_args(l, mb, sA);
                 // (last_cls_bwd = 2 in the last block: on the CLS rows, where this step's clears covered it)
-                if (lc && d1_clean && !ec && lc_d1_gathered(l, mb, sA, d1g)) {
-                    d1 = d1g;
-                } else {
-                    d1.A = sA + r0 * C; d1.lda = C; dgrad_b(d1, P_FCPROJW, l, C);
-                    d1.C = dfch + r0 * 4 * C; d1.ldc = 4 * C; d1.aux = a.fchd + r0 * 4 * C; d1.ldaux = 4 * C;
-                    d1.M = (int)R; d1.N = 4 * C; d1.K = C; d1.epi = EPI_BF16_MUL;
-                    fcb_rows = gemm_colsum_rows(d1, fp8());  // partial rows per micro-batch (engine-dependent)
-                    d1.colsum_part = sg_rows(l, sg_fcb) + (long long)mb * fcb_rows * 4 * C;
-                }
+                if (lc && d1_clean && !ec) d1_gather(d1);
                 if (ec) {  // dfch only as its row (mx_out) and column MX forms
                     d1.C = nullptr;
                     d1.mxc_q = dfchc.q; d1.mxc_s = dfchc.s; d1.mxc_ld = kp_tok; d1.mxc_off = r0;
@@ -1458,8 +1508,7 @@ struct Trainer {
                        rc && !resa_pre ? &dcol[0] : nullptr, resa_pre ? -1 : EV_RESA);
                 if (ec && two_streams) VIT_HIP(hipEventRecord(mev[mb][EV_DFCH], ms[mb]));  // dfchc final
             }
-            if (rc) wgrad(TC_FCPROJ_WGRAD, rbA, C, a.fchg, 4 * C, G(P_FCPROJW, l), EV_RESA, EV_W1, &dcol[0],
-                          ec ? &c_fchg : nullptr);
+            if (rc) w_fcproj();
             // fc: dln2 = dfch . fcw;  fcw += dfch^T . ln2
             wgrad(TC_FC_WGRAD, dfch, 4 * C, a.ln2, C, G(P_FCW, l), EV_DFCH, EV_W2, ec ? &dfchc : nullptr,
                   rc ? &c_ln2 : nullptr, kper);
@@ -1470,33 +1519,11 @@ struct Trainer {
                 d2.C = dln_bf + r0 * C; d2.ldc = rs * C; d2.M = Mr; d2.N = C; d2.K = 4 * C; d2.epi = EPI_BF16_STORE;
                 d2.rows_gathered = lcg;
                 gemm_w(TC_FC_DGRAD, d2, P_FCW, l, true, mb, ms[mb], fuse_mx ? PRE_EPI : PRE_NONE);
-                // ln2 backward + residual: dres2 = dres3 + LN2'(dln2); attproj_b += colsum(dres2)
                 after_wgrad(EV_W3, ms[mb]);  // the previous layer's attproj wgrad has read rbB
-                tbeg(TC_LN_BWD, 0, ms[mb]);
-                if (lbm) {  // + dres2's MX forms (the attproj dgrad's A operand, the attproj wgrad's dout)
-                    ln_backward_bf16_stream_mx(rbB + r0 * C, loB + r0 * C, rbA + r0 * C, loA + r0 * C, G(P_LN2W, l),
-                                               G(P_LN2B, l), G(P_ATTPROJB, l), dln_bf + r0 * C, a.res2 + r0 * C,
-                                               P(P_LN2W, l), a.ln2_mean + r0, a.ln2_rstd + r0, R, C, ms[mb],
-                                               sg_rows(l, sg_ln2) + (long long)mb * ln_bwd_blocks(R) * 3 * C,
-                                               act_q[mb], act_s[mb], dcol[1].q, dcol[1].s, kp_tok, r0, mb_ntok(mb, R),
-                                               lnb_scr[mb]);
-                    if (two_streams) VIT_HIP(hipEventRecord(mev[mb][EV_RESB], ms[mb]));
-                } else if (dp) {  // + dres2 scaled by the attention branch's rows; attproj_b from the products
-                    ln_backward_bf16_stream_dp(rbB + r0 * C, loB + r0 * C, dres_s2 + r0 * C, dp_scale(l, 0, r0),
-                                               rbA + r0 * C, loA + r0 * C, G(P_LN2W, l), G(P_LN2B, l),
-                                               G(P_ATTPROJB, l), dln_bf + r0 * C, a.res2 + r0 * C, P(P_LN2W, l),
-                                               a.ln2_mean + r0, a.ln2_rstd + r0, R, C, ms[mb],
-                                               sg_rows(l, sg_ln2) + (long long)mb * ln_bwd_blocks(R) * 3 * C);
-                } else {
-                    ln_backward_bf16_stream(rbB + r0 * C, loB + r0 * C, rbA + r0 * C, loA + r0 * C, G(P_LN2W, l),
-                                            G(P_LN2B, l), G(P_ATTPROJB, l), dln_bf + r0 * C, a.res2 + r0 * C,
-                                            P(P_LN2W, l), a.ln2_mean + r0, a.ln2_rstd + r0, R, C, ms[mb],
-                                            sg_rows(l, sg_ln2) + (long long)mb * ln_bwd_blocks(R) * 3 * C);
-                }
-                tend();
+                ln_bwd(l, mb, true, R);
             }
             // attproj
-            if (!rc) wgrad(TC_PROJ_WGRAD, sB, C, a.atty, C, G(P_ATTPROJW, l), EV_RESB, EV_W3, nullptr, nullptr, kper);
+            if (!rc) w_attproj();
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d3;
@@ -1514,61 +1541,39 @@ struct Trainer {
                                     attn_part + (long long)attn_backward_ws_floats(mb * Bm, T, C, NH), true);
                 tend();
             }
-            if (rc) wgrad(TC_PROJ_WGRAD, rbB, C, a.atty, C, G(P_ATTPROJW, l), EV_RESB, EV_W3, &dcol[1], &c_atty);
+            if (rc) w_attproj();
             // qkv
-            if (!rc) wgrad(TC_QKV_WGRAD, dqkv, 3 * C, a.ln1, C, G(P_QKVW, l), EV_DQKV, EV_W4);
+            if (!rc) w_qkv();
             for (int mb = 0; mb < nmb; mb++) {
                 const long long r0 = mb * R;
                 GemmArgs d4;
                 d4.A = dqkv + r0 * 3 * C; d4.lda = 3 * C; dgrad_b(d4, P_QKVW, l, 3 * C);
                 d4.C = dln_bf + r0 * C; d4.ldc = C; d4.M = (int)R; d4.N = C; d4.K = 3 * C; d4.epi = EPI_BF16_STORE;
                 gemm_w(TC_QKV_DGRAD, d4, P_QKVW, l, true, mb, ms[mb], PRE_NONE, false, rc ? &dcol[2] : nullptr, EV_DQKV);
-                // ln1 backward: dres = dres2 + LN1'(dln1); fcproj_b of layer l-1 += colsum(dres)
                 after_wgrad(EV_W1, ms[mb]);  // this layer's fcproj wgrad has read rbA
-                tbeg(TC_LN_BWD, 0, ms[mb]);
-                if (lbm && l > 0) {  // + dres3's MX forms for layer l-1's fcproj dgrad / wgrad
-                    ln_backward_bf16_stream_mx(rbA + r0 * C, loA + r0 * C, rbB + r0 * C, loB + r0 * C, G(P_LN1W, l),
-                                               G(P_LN1B, l), G(P_FCPROJB, l - 1), dln_bf + r0 * C, xl + r0 * C,
-                                               P(P_LN1W, l), a.ln1_mean + r0, a.ln1_rstd + r0, R, C, ms[mb],
-                                               sg_rows(l, sg_ln1) + (long long)mb * ln_bwd_blocks(R) * 3 * C,
-                                               act_q[mb], act_s[mb], dcol[0].q, dcol[0].s, kp_tok, r0, mb_ntok(mb, R),
-                                               lnb_scr[mb]);
-                    if (two_streams) VIT_HIP(hipEventRecord(mev[mb][EV_RESA], ms[mb]));
-                } else if (dp && l > 0) {  // + dres3 of layer l-1 scaled by its MLP branch's rows; its fcproj_b
-                    ln_backward_bf16_stream_dp(rbA + r0 * C, loA + r0 * C, dres_s + r0 * C, dp_scale(l - 1, 1, r0),
-                                               rbB + r0 * C, loB + r0 * C, G(P_LN1W, l), G(P_LN1B, l),
-                                               G(P_FCPROJB, l - 1), dln_bf + r0 * C, xl + r0 * C, P(P_LN1W, l),
-                                               a.ln1_mean + r0, a.ln1_rstd + r0, R, C, ms[mb],
-                                               sg_rows(l, sg_ln1) + (long long)mb * ln_bwd_blocks(R) * 3 * C);
-                } else {
-                    ln_backward_bf16_stream(rbA + r0 * C, loA + r0 * C, rbB + r0 * C, loB + r0 * C, G(P_LN1W, l),
-                                            G(P_LN1B, l), l > 0 ? G(P_FCPROJB, l - 1) : nullptr, dln_bf + r0 * C,
-                                            xl + r0 * C, P(P_LN1W, l), a.ln1_mean + r0, a.ln1_rstd + r0, R, C, ms[mb],
-                                            sg_rows(l, sg_ln1) + (long long)mb * ln_bwd_blocks(R) * (l > 0 ? 3 : 2) * C);
-                }
-                tend();
+                ln_bwd(l, mb, false, R);
             }
-            if (rc) wgrad(TC_QKV_WGRAD, dqkv, 3 * C, a.ln1, C, G(P_QKVW, l), EV_DQKV, EV_W4, &dcol[2], &c_ln1);
+            if (rc) w_qkv();
             sg_finalize(l, R);
             chunk_done(L - l);
         }
         mb_join();
-        if (two_streams) {  // every wgrad done before the slab workspace / grads are reused
-            VIT_HIP(hipEventRecord(bev[EV_JOIN], s2));
-            VIT_HIP(hipStreamWaitEvent(s, bev[EV_JOIN], 0));
-        }
-        // patch embedding backward (encoder_backward, train_vit.rs:371 -> ViT)
+        if (two_streams) order(bev[EV_JOIN], s2, s);  // every wgrad done before the slab workspace / grads are reused
+        patch_backward();
+        chunk_done(L + 1);
+    }
+    // patch embedding backward (encoder_backward, train_vit.rs:371 -> ViT) from the final dres in dres_bf / dres_lo
+    void patch_backward() {
         tbeg(TC_PATCH_BWD, 2.0 * B * NP * (double)KP * C);
         // cls / position / patch-bias gradients (psg: three small kernels, 43 us) on s2 beside the
         // patch weight gradient on s; s waits for them before the chunk is final
         const bool psg_side = two_streams && lowp();
         if (psg_side) {
-            VIT_HIP(hipEventRecord(bev[EV_SG], s));
-            VIT_HIP(hipStreamWaitEvent(s2, bev[EV_SG], 0));
-            patch_small_grads(G(P_CLS), G(P_WPE), G(P_PATCH_B), rbA, loA, B, T, C, s2, pos_sums, psg_part);
+            order(bev[EV_SG], s, s2);
+            patch_small_grads(G(P_CLS), G(P_WPE), G(P_PATCH_B), dres_bf, dres_lo, B, T, C, s2, pos_sums, psg_part);
             VIT_HIP(hipEventRecord(bev[EV_JOIN], s2));
         }
-        patch_gather_bf16(dpatch_bf, rbA, B, NP, C, s);
+        patch_gather_bf16(dpatch_bf, dres_bf, B, NP, C, s);
         GemmArgs w;
         w.A = dpatch_bf; w.lda = C; w.a_kcontig = false;
         w.B = patches_bf; w.ldb = KPP; w.b_kcontig = false;
@@ -1587,9 +1592,8 @@ struct Trainer {
         if (psg_side)
             VIT_HIP(hipStreamWaitEvent(s, bev[EV_JOIN], 0));
         else
-            patch_small_grads(G(P_CLS), G(P_WPE), G(P_PATCH_B), rbA, loA, B, T, C, s, pos_sums, psg_part);
+            patch_small_grads(G(P_CLS), G(P_WPE), G(P_PATCH_B), dres_bf, dres_lo, B, T, C, s, pos_sums, psg_part);
         tend();
-        chunk_done(L + 1);
     }
 
     // ------------------------------------------------------------------ fp32 reference path
@@ -1710,16 +1714,10 @@ struct Trainer {
     // ms[1..nmb)): s_comm waits for all of them.  early_on and clip_live each imply two_streams && lowp()
     // (vit_trainer_train_step, clip_overlap_on), so their chunks always take the side-stream events.
     void chunk_fan_in(int c) {
-        VIT_HIP(hipEventRecord(chunk_ev[c], s));
-        VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev[c], 0));
+        order(chunk_ev[c], s, s_comm);
         if (!(two_streams && lowp())) return;
-        VIT_HIP(hipEventRecord(chunk_ev2[c], s2));
-        VIT_HIP(hipStreamWaitEvent(s_comm, chunk_ev2[c], 0));
-        for (int k = 1; k < nmb; k++) {
-            hipEvent_t e = chunk_evm[(size_t)c * MAXMB + k];
-            VIT_HIP(hipEventRecord(e, ms[k]));
-            VIT_HIP(hipStreamWaitEvent(s_comm, e, 0));
-        }
+        order(chunk_ev2[c], s2, s_comm);
+        for (int k = 1; k < nmb; k++) order(chunk_evm[(size_t)c * MAXMB + k], ms[k], s_comm);
     }
     // Global-norm gradient clipping (option of vit_trainer_set_grad_clip).  The sum of
     // squares of the gradients is taken per gradient chunk (the chunk_off ranges, in every mode, so
@@ -1771,8 +1769,7 @@ struct Trainer {
     // the clip record of the gradients as they stand (after pre_side_wait and finish_allreduce), on s
     void clip_norm() {
         if (clip_comm_busy) {
-            VIT_HIP(hipEventRecord(comm_done, s_comm));
-            VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
+            order(comm_done, s_comm, s);
             clip_comm_busy = false;
         }
         if (!clip_parts_valid)
@@ -1813,8 +1810,7 @@ struct Trainer {
                 VIT_HIP(hipMemcpyAsync(dp_snap, grads, (size_t)arena_elems * 4, hipMemcpyDeviceToDevice, s));
             return;
         }
-        VIT_HIP(hipEventRecord(comm_done, s_comm));
-        VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
+        order(comm_done, s_comm, s);
     }
 
     // upload one uint8 batch (host) and normalise it into `pixels` (include/vit_data.h)
@@ -1855,8 +1851,7 @@ struct Trainer {
             }
         }
         if (lab) VIT_HIP(hipMemcpyAsync(lab_stage[k], lab, (size_t)B * 4, hipMemcpyHostToDevice, s_copy));
-        VIT_HIP(hipEventRecord(u8_copied[k], s_copy));
-        VIT_HIP(hipStreamWaitEvent(s, u8_copied[k], 0));
+        order(u8_copied[k], s_copy, s);
         has_targets = lab != nullptr;
         mixed = false;
         erased = false;
@@ -1909,8 +1904,7 @@ struct Trainer {
     // s behind the optimizer work of the side streams (early SGD on s_comm, the side pre-work on s2)
     void ema_join() {
         pre_side_wait();
-        VIT_HIP(hipEventRecord(comm_done, s_comm));
-        VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
+        order(comm_done, s_comm, s);
     }
     void ema_set_decay(float d) {
         ema_d = d;
@@ -2223,8 +2217,7 @@ struct Trainer {
         if (early_done) {  // every chunk already updated on s_comm (train_step with early SGD)
             early_done = false;
             pre_side_wait();
-            VIT_HIP(hipEventRecord(comm_done, s_comm));
-            VIT_HIP(hipStreamWaitEvent(s, comm_done, 0));
+            order(comm_done, s_comm, s);
             if (sgdm_on()) sgd_steps++;
             refresh_transposed();
             return;
@@ -2508,8 +2501,7 @@ int vit_trainer_zero_grad(vit_trainer_t* h) {
     t.clip_parts_valid = false;
     // the previous step's all-reduce must be done with the arena before it is cleared
     if (t.comm) {
-        VIT_HIP(hipEventRecord(t.comm_done, t.s_comm));
-        VIT_HIP(hipStreamWaitEvent(t.s, t.comm_done, 0));
+        t.order(t.comm_done, t.s_comm, t.s);
     }
     if (t.pre_side_on()) {  // on s2 beside the forward; the backward waits for it
         hipStream_t zs = t.pre_side_begin();
