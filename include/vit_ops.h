@@ -73,7 +73,9 @@ enum {
                                         kernels of vit_trainer_mix_batch are in no family */
     VIT_HIT_SGDM = 97,               /* momentum SGD: every momentum instantiation of the optimizer kernels
                                         (vit_trainer_set_sgd) and sgd_momentum_step */
-    VIT_HIT_COUNT = 98
+    VIT_HIT_ACCUM = 98,              /* gradient accumulation: a launch of grad_accumulate's kernel (the op, or the
+                                        trainer's sums under vit_trainer_set_grad_accum; its first copy is not one) */
+    VIT_HIT_COUNT = 99
 };
 int vit_kernel_hits(long long* out, int n); /* copies min(n, VIT_HIT_COUNT); returns VIT_HIT_COUNT */
 void vit_kernel_hits_reset(void);
@@ -167,6 +169,13 @@ void grad_sumsq(double* out, const float* x, long long n);
  * scalar tail for n % 4 (all scalar otherwise).  No reference counterpart: the update the trainer's optimizer
  * kernels fuse for vit_trainer_set_ema, stand-alone; fp32-mode SGD launches it. */
 void ema_update(float* ema, const float* params, long long n, float decay);
+/* out[i] = fl32(a[i] + b[i]) for i < n: one fp32 addition per element, numpy's fp32 `a + b`.  Device pointers,
+ * any n >= 0 (n == 0 launches nothing), any 4-byte alignment.  out may be exactly a or exactly b (an in-place
+ * sum); any other overlap of out with an input is an error.  16-byte accesses over n / 4 float4s when all three
+ * pointers are 16-byte aligned and a scalar tail for n % 4 (all scalar otherwise): the same values either way.
+ * No atomics.  No reference counterpart: the summing pass of the trainer's gradient accumulation
+ * (vit_trainer_set_grad_accum), stand-alone. */
+void grad_accumulate(float* out, const float* a, const float* b, long long n);
 /* One LAMB step (vit_trainer.h vit_trainer_step_lamb) of one tensor as one segment: m, v
  * advanced as AdamW's step t does, u = mh / (sqrt(vh) + eps) + weight_decay * p, the norms of p and u in double
  * (fixed order), r = |p| / |u| where the tensor is adapted (weight_decay != 0, or flags & 1 = always adapt) and

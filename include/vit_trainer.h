@@ -302,6 +302,44 @@ int vit_trainer_get_sgd_info(vit_trainer_t* t, float* momentum, float* dampening
                              int* nesterov, long long* steps);
 /* canonical host copy of the momentum buffer; synchronous; an error before the first momentum step */
 int vit_trainer_get_momentum(vit_trainer_t* t, float* host);
+/* ---- gradient accumulation over micro-batches: with steps = N > 1 the calls of
+ *      vit_trainer_backward are counted in windows of N and their gradients summed on the device, so that one
+ *      optimizer step sees a batch N times the one that fits.  `done` is the number of micro-steps in the open
+ *      window: 0 = no window is open, N = the window is complete and not yet consumed.
+ *        backward 1 of a window:   acc = g          (acc: one more fp32 arena of arena_elems floats, allocated by
+ *                                                    the first such backward and counted in vit_trainer_device_bytes)
+ *        backward k, 1 < k < N:    acc = fl32(acc + g)   per element
+ *        backward N:               g = fl32(acc + g), written into the gradient arena itself
+ *      so after backward N the gradient arena holds (((g1 + g2) + g3) + ... + gN), each sum rounded to fp32 once,
+ *      in this fixed order: a function of the micro-batches and their order only, not of streams, chunks or the
+ *      form that ran (option "accum_overlap").  The arena's padding stays zero.  A backward while done == N opens
+ *      a new window (done = 1).  Everything at step time reads the gradient arena as always, so the clip norm and
+ *      factor (vit_trainer_set_grad_clip) are those of the accumulated gradient, parameter groups, the EMA, momentum
+ *      SGD, AdamW and LAMB need nothing more, and vit_trainer_get_grads returns the micro-batch's own gradient
+ *      mid-window and the sum after backward N.
+ *      Scaling is the caller's: pass b_global = N * batch * world to vit_trainer_forward / _train_step
+ *      (dloss = 1 / b_global), and the sum is the gradient of the mean loss over the whole window.
+ *      vit_trainer_step, _step_adamw and _step_lamb return non-zero with vit_last_error ("... gradient
+ *      accumulation: micro-step k of N") and change nothing while 0 < done < N; otherwise they run as always
+ *      and set done = 0.  vit_trainer_train_step: a call that leaves done < N does zero_grad + forward +
+ *      backward + accumulate and returns 0 without an update; the call that completes the window also steps
+ *      (only that call may take the early per-chunk SGD, each chunk's update behind the chunk's final sum).
+ *      The mix, the erase, the one-shot drop-path table, the augment plan and vit_trainer_mean_loss stay per
+ *      micro-batch.  vit_trainer_eval and forwards of a batch without labels do not count and do not touch acc.
+ *      vit_trainer_save_checkpoint is an error mid-window and writes nothing; vit_trainer_load_checkpoint sets
+ *      done = 0.  Data parallelism: backwards 1 .. N-1 issue no all-reduce (torch's no_sync); backward N reduces
+ *      the accumulated gradient, per chunk behind the chunk's final sum with overlap on, whole at step time
+ *      otherwise.  Every rank must set the same N.
+ *      steps == 1, or never set: nothing is allocated, and the launches, their order and the checkpoint bytes
+ *      are those of a trainer without the feature. ---- */
+/* steps >= 1; 1 = off (the default).  Any call, also with the same value, abandons an open window (done = 0):
+ * the way out of one.  steps < 1: non-zero + vit_last_error, the previous setting stays.  Waits for the work in
+ * flight.  A hyper-parameter: persists across steps, not written to checkpoints. */
+int vit_trainer_set_grad_accum(vit_trainer_t* t, int steps);
+/* *steps and *done as above; either pointer may be NULL */
+int vit_trainer_get_grad_accum_info(vit_trainer_t* t, int* steps, int* done);
+/* canonical host copy of the accumulator acc while 0 < done < N; an error otherwise; synchronous */
+int vit_trainer_get_grad_accum(vit_trainer_t* t, float* host);
 /* canonical host copies of m, v (either may be NULL) and the step count; synchronous */
 int vit_trainer_get_adamw_state(vit_trainer_t* t, float* m, float* v, int* step);
 /* eval: forward of the current batch, then top-1 per image on the device.
@@ -350,6 +388,10 @@ int vit_trainer_set_concurrency(vit_trainer_t* t, int on);
  *      gradient clipping on, bf16 / fp8 and concurrency on, 1 takes each gradient chunk's partial
  *      sums of squares on the side (all-reduce) stream as soon as the backward has finished the
  *      chunk, 0 takes them all at step time on the main stream (same bits either way),
+ *      "accum_overlap" = -1 (default: auto = 0 in bf16 mode, 1 in fp8 mode, measured): under
+ *      gradient accumulation, bf16 / fp8 and concurrency on, 1 sums each gradient chunk on the side
+ *      (all-reduce) stream as soon as the backward has finished the chunk, 0 sums the whole arena in one
+ *      launch behind the backward (same bits either way),
  *      "last_cls" = 1 (default; bf16 mode only, ignored in fp32 and fp8 mode): the classifier head reads
  *      only the CLS row of each image, so the last block's attention projection, LayerNorm 2, fc + GELU
  *      and fcproj and the fc / attention-projection input gradients run on the B CLS rows instead of all

@@ -28,6 +28,7 @@ from . import droppath  # noqa: E402  (stochastic depth: the per-step table draw
 from . import ema  # noqa: E402  (EMA of the weights: the warm-up schedule and the numpy statement)
 from . import erase  # noqa: E402  (random erasing: the box draw and the numpy statement)
 from . import sgd  # noqa: E402  (momentum SGD: the timm presets and the numpy statement)
+from . import accum  # noqa: E402  (gradient accumulation: the window plan and the numpy statement)
 
 VIT_FP32, VIT_BF16, VIT_FP8 = 0, 1, 2
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2  # include/vit_trainer.h VIT_MIX_*
@@ -108,6 +109,7 @@ _SIGS = {
     "sgd_step": (None, [P, P, LL, F]),
     "grad_sumsq": (None, [P, P, LL]),
     "ema_update": (None, [P, P, LL, F]),
+    "grad_accumulate": (None, [P, P, P, LL]),
     "lamb_step": (None, [P, P, P, P, LL, F, F, F, F, F, I, I, P]),
     "sgd_momentum_step": (None, [P, P, P, LL, F, F, F, F, I, I]),
     # bf16 extensions
@@ -182,6 +184,9 @@ _SIGS = {
     "vit_trainer_get_sgd_info": (I, [P, ctypes.POINTER(F), ctypes.POINTER(F), ctypes.POINTER(F), ctypes.POINTER(I),
                                      ctypes.POINTER(LL)]),
     "vit_trainer_get_momentum": (I, [P, P]),
+    "vit_trainer_set_grad_accum": (I, [P, I]),
+    "vit_trainer_get_grad_accum_info": (I, [P, ctypes.POINTER(I), ctypes.POINTER(I)]),
+    "vit_trainer_get_grad_accum": (I, [P, P]),
     "vit_trainer_set_drop_path": (I, [P, P]),
     "vit_trainer_get_drop_path": (I, [P, P, ctypes.POINTER(I)]),
     "vit_drop_path_draw": (I, [ctypes.c_ulonglong, LL, I, I, F, I, P]),
@@ -263,6 +268,7 @@ HIT_AUGMENT = 91  # + 0 statistics / LUT, 1 in-place apply, 2 out-of-place apply
 HIT_EMA = 95  # a launch that advances an EMA of the weights (fused optimizer kernel or ema_update)
 HIT_ERASE = 96  # random erasing: one launch per call that has a non-empty box
 HIT_SGDM = 97  # momentum SGD: a momentum instantiation of the optimizer kernels or sgd_momentum_step
+HIT_ACCUM = 98  # gradient accumulation: a launch of grad_accumulate's kernel (the op or the trainer's sums)
 
 
 def kernel_hits():
@@ -363,6 +369,12 @@ def call(name, *args):
     getattr(L, name)(*cargs)
     L.vit_sync()
     check(name)
+
+
+def grad_accumulate(out, a, b, n):
+    """out[i] = fl32(a[i] + b[i]) for i < n on device buffers (DeviceArray, or a device address as an int for a
+    view at an offset); out may be a or b (grad_accumulate, include/vit_ops.h); synchronous."""
+    call("grad_accumulate", out, a, b, int(n))
 
 
 def augment_u8(images, plan, fill=(0, 0, 0)):
@@ -699,6 +711,7 @@ class ViT:
         self.num_parameters = int(L.vit_trainer_num_params(self.h))
         assert self.num_parameters == cfg.num_params()
         self.mean_loss = -1.0
+        self.accum_steps = 1  # set_grad_accum: the default b_global of forward / train_step is B * accum_steps
 
     @classmethod
     def build(cls, cfg, batch, precision=VIT_BF16, params=None, device=0):
@@ -820,13 +833,13 @@ class ViT:
     def forward(self, pixels=None, targets=None, b_global=None):
         if pixels is not None:
             self.set_batch(pixels, targets)
-        self._ok(lib().vit_trainer_forward(self.h, int(b_global or self.B)), "forward")
+        self._ok(lib().vit_trainer_forward(self.h, int(b_global or self.B * self.accum_steps)), "forward")
         self.mean_loss = float(lib().vit_trainer_mean_loss(self.h))
         check("mean_loss")
         return self.mean_loss
 
     def forward_async(self, b_global=None):
-        self._ok(lib().vit_trainer_forward(self.h, int(b_global or self.B)), "forward")
+        self._ok(lib().vit_trainer_forward(self.h, int(b_global or self.B * self.accum_steps)), "forward")
 
     def zero_grad(self):
         self._ok(lib().vit_trainer_zero_grad(self.h), "zero_grad")
@@ -977,6 +990,27 @@ class ViT:
         self._ok(lib().vit_trainer_get_momentum(self.h, out.ctypes.data_as(P)), "get_momentum")
         return out
 
+    # ---- gradient accumulation (include/vit_trainer.h)
+    def set_grad_accum(self, steps):
+        """Sum the gradients of `steps` backwards on the device before an optimizer step (1 = off); any call
+        abandons an open window.  forward / forward_async / train_step then default b_global to B * steps: on
+        several ranks pass b_global = steps * B * world yourself (vit_trainer_set_grad_accum; accum.plan)."""
+        self._ok(lib().vit_trainer_set_grad_accum(self.h, int(steps)), "set_grad_accum")
+        self.accum_steps = int(steps)
+
+    def grad_accum_info(self):
+        """(steps, done): done micro-steps in the open window; 0 = none open, steps = complete, not yet consumed."""
+        n, k = I(), I()
+        self._ok(lib().vit_trainer_get_grad_accum_info(self.h, ctypes.byref(n), ctypes.byref(k)), "get_grad_accum_info")
+        return int(n.value), int(k.value)
+
+    def grad_accum(self):
+        """The accumulator, canonical order, while a window is open (vit_trainer_get_grad_accum; synchronous;
+        raises otherwise)."""
+        out = np.empty(self.num_parameters, dtype=np.float32)
+        self._ok(lib().vit_trainer_get_grad_accum(self.h, out.ctypes.data_as(P)), "get_grad_accum")
+        return out
+
     def adamw_state(self):
         """(m, v, t) in canonical order."""
         m = np.empty(self.num_parameters, np.float32)
@@ -1002,7 +1036,7 @@ class ViT:
         self._ok(lib().vit_trainer_load_checkpoint(self.h, os.fsencode(path)), "load_checkpoint")
 
     def train_step(self, lr, b_global=None):
-        self._ok(lib().vit_trainer_train_step(self.h, float(lr), int(b_global or self.B)),
+        self._ok(lib().vit_trainer_train_step(self.h, float(lr), int(b_global or self.B * self.accum_steps)),
                  "train_step")
 
     def logits(self):

@@ -67,6 +67,21 @@ __global__ void ema_update_k(float* __restrict__ e, const float* __restrict__ p,
     }
     for (long long i = n4 * 4 + tid; i < n; i += nth) e[i] = ema_blend(e[i], p[i], d, omd);
 }
+// out = fl32(a + b) (grad_accumulate, include/vit_ops.h): n4 float4s, then the elements
+// [4 n4, n) as scalars; 12 B of HBM traffic per element.  out may be exactly a or exactly b (the trainer sums
+// in place), so no pointer is __restrict__: every thread loads the elements it owns before it stores them,
+// and no other thread touches them.  The loop of ema_update_k, which it matches in bytes per second
+// (DESIGN.md §20): one float4 per array in flight per thread, the grid's occupancy hides the latency.
+__global__ void grad_accumulate_k(float* out, const float* a, const float* b, long long n4, long long n) {
+    const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long nth = (long long)gridDim.x * blockDim.x;
+    for (long long i = tid; i < n4; i += nth) {
+        const float4 av = reinterpret_cast<const float4*>(a)[i];
+        const float4 bv = reinterpret_cast<const float4*>(b)[i];
+        reinterpret_cast<float4*>(out)[i] = make_float4(av.x + bv.x, av.y + bv.y, av.z + bv.z, av.w + bv.w);
+    }
+    for (long long i = n4 * 4 + tid; i < n; i += nth) out[i] = a[i] + b[i];
+}
 
 // ------------------------------------------------------------------ sum of squares (gradient norm)
 // slots[blockIdx.x] = sum of x[i]^2 over this workgroup's grid-stride share of x[0..n): every element
@@ -964,6 +979,14 @@ void ema_update_on(float* e, const float* p, long long n, float d, float omd, hi
     after_launch("ema_update");
     count_hit(VIT_HIT_EMA);
 }
+void grad_accumulate_on(float* out, const float* a, const float* b, long long n, hipStream_t s) {
+    if (n <= 0) return;
+    const bool vec = (((uintptr_t)out | (uintptr_t)a | (uintptr_t)b) & 15) == 0;
+    const long long n4 = vec ? n / 4 : 0;
+    grad_accumulate_k<<<grid_for(vec ? (n + 3) / 4 : n, 256), 256, 0, s>>>(out, a, b, n4, n);
+    after_launch("grad_accumulate");
+    count_hit(VIT_HIT_ACCUM);
+}
 // a function of n alone (not of the device or of anything scheduling-dependent): one workgroup per
 // 4096 elements (four 16-byte loads per thread), at most 1024
 int sumsq_blocks(long long n) {
@@ -1262,6 +1285,17 @@ void ema_update(float* ema, const float* params, long long n, float decay) {
     VIT_REQUIRE(n >= 0 && decay >= 0.f && decay <= 1.f, "ema_update: n %lld, decay %g of [0, 1]", n, (double)decay);
     VIT_REQUIRE(n == 0 || (ema && params), "ema_update: null pointer");
     ema_update_on(ema, params, n, decay, (float)(1.0 - (double)decay), stream());
+}
+void grad_accumulate(float* out, const float* a, const float* b, long long n) {
+    VIT_REQUIRE(n >= 0, "grad_accumulate: n %lld", n);
+    VIT_REQUIRE(n == 0 || (out && a && b), "grad_accumulate: null pointer");
+    for (const float* x : {a, b}) {  // out is exactly an input or apart from it
+        const uintptr_t o = (uintptr_t)out, i = (uintptr_t)x;
+        const unsigned long long d = o > i ? o - i : i - o;
+        VIT_REQUIRE(d == 0 || d >= (unsigned long long)n * 4,
+                    "grad_accumulate: out overlaps an input partially (%llu bytes apart, n %lld)", d, n);
+    }
+    grad_accumulate_on(out, a, b, n, stream());
 }
 void grad_sumsq(double* out, const float* x, long long n) {
     VIT_REQUIRE(n >= 0, "grad_sumsq: n %lld", n);

@@ -54,6 +54,8 @@ int ln_bwd_blocks(long long rows);
 void convert_f2bf(bf16_t* out, const float* inp, long long n, hipStream_t s);
 // e = ema_blend(e, p) over n elements on s (the body of ema_update, include/vit_ops.h; common.h ema_blend)
 void ema_update_on(float* e, const float* p, long long n, float d, float omd, hipStream_t s);
+// out = fl32(a + b) over n elements on s (the body of grad_accumulate, include/vit_ops.h); out may be a or b
+void grad_accumulate_on(float* out, const float* a, const float* b, long long n, hipStream_t s);
 // sum of squares in double, deterministic (the body of grad_sumsq, include/vit_ops.h):
 // sumsq_partials writes sumsq_blocks(n) per-workgroup partial sums (a function of n alone; 0 for
 // n <= 0, then nothing is launched) to slots; sumsq_finish / clip_finish sum nslots of them in slot

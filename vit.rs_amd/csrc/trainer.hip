@@ -1704,8 +1704,8 @@ struct Trainer {
     bool early_sgd_on() const { return early_sgd < 0 ? fp8() : early_sgd != 0; }
     bool early_on = false, early_done = false;
     float early_lr = 0.f;
-    void sgd_chunk(int c) {
-        chunk_fan_in(c);
+    void sgd_chunk(int c, bool fanned = false) {  // fanned: s_comm already waits for the chunk (its accumulate)
+        if (!fanned) chunk_fan_in(c);
         // the chunk's flat range, or its tiles of the whole-arena tiled kernel: elementwise, the one pass's bits
         optimizer_launch(sgd_kind(), optim_args(c, early_lr, false, groups_on), groups_on, s_comm);
         if (!ema_fuse(sgdm_on())) ema_behind(c, s_comm);
@@ -1778,19 +1778,75 @@ struct Trainer {
         clip_parts_valid = false;
         clip_have_norm = true;
     }
+    // Gradient accumulation (vit_trainer_set_grad_accum): with acc_steps = N > 1 the backwards
+    // are counted in windows of N.  Backward 1 copies the gradient arena into acc (one more fp32 arena,
+    // allocated by the first such backward), backward k < N adds the arena to acc, backward N adds acc into the
+    // arena itself: grads then holds (((g1 + g2) + g3) + ... + gN), one fp32 addition per term in this order,
+    // and everything at step time (the clip norm, every optimizer launch, the all-reduce, get_grads) reads it
+    // as it reads any gradient.  The padding is zero in every term and stays zero.
+    // Two forms of the same elementwise statement (option "accum_overlap"): plain, one launch over the arena on
+    // s at the end of the backward; overlapped, chunk c's range on s_comm at chunk_done(c) behind
+    // chunk_fan_in(c), beside the rest of the backward (no stream of its own: see early_sgd).  The backward that
+    // completes a window takes the per-chunk form whenever chunk_done has a consumer of the chunk (the early SGD,
+    // the live clip partials, the overlapped all-reduce, in any precision mode): that consumer runs on s_comm
+    // behind the chunk's final sum.  Backwards 1 .. N-1 have no consumer: no early SGD, no live partials, no
+    // all-reduce (torch's no_sync).  After a backward that launched on s_comm, s is ordered behind s_comm
+    // (vit_trainer_backward): the next zero_grad (on s, or on s2 behind s: pre_side_begin), the next backward's
+    // writers, the step and the readbacks all follow s.
+    int acc_steps = 1, acc_done = 0;
+    int acc_overlap = -1;
+    float* acc = nullptr;
+    int acc_k = 0;             // the running backward is number acc_k of its window (0: accumulation is off)
+    bool acc_chunked = false;  // ... and sums per chunk on s_comm
+    bool acc_comm_busy = false;
+    bool acc_overlap_on() const {
+        if (!(lowp() && two_streams && !timing && s2)) return false;
+        // auto = plain in bf16 mode, overlapped in fp8 mode (as early_sgd).  Measured (tools/bench_accum.py, same
+        // process, N = 4, profiles/grad_accum_ab.txt), ms per micro-step in two processes: ViT-B/16 bf16 plain
+        // 34.10 / 34.15 vs overlapped 34.18 / 34.22 (plain ahead in both, the ranges disjoint in one), ViT-H/14 fp8
+        // plain 113.97 / 114.46 vs overlapped 113.58 / 113.79 (overlapped ahead by 0.3 and 0.6 %, the ranges disjoint
+        // in one; ahead in both processes of an earlier run on another box too)
+        return acc_overlap < 0 ? fp8() : acc_overlap != 0;
+    }
+    bool acc_open() const { return acc_done > 0 && acc_done < acc_steps; }
+    // false, with the error set, while a window is open: the optimizer steps and the checkpoint writer
+    bool acc_closed(const char* who) {
+        if (!acc_open()) return true;
+        set_error("%s: gradient accumulation: micro-step %d of %d", who, acc_done, acc_steps);
+        return false;
+    }
+    // the number the next backward has in its window (0: off)
+    int acc_next() const { return acc_steps > 1 ? (acc_done >= acc_steps ? 1 : acc_done + 1) : 0; }
+    // elements [o, o + n) of the running backward's statement, on st
+    void acc_range(long long o, long long n, hipStream_t st) {
+        if (acc_k == 1)
+            VIT_HIP(hipMemcpyAsync(acc + o, grads + o, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        else if (acc_k < acc_steps)
+            grad_accumulate_on(acc + o, acc + o, grads + o, n, st);
+        else
+            grad_accumulate_on(grads + o, acc + o, grads + o, n, st);
+    }
     void chunk_done(int c) {
+        bool fanned = false;
+        if (acc_chunked) {
+            chunk_fan_in(c);
+            fanned = true;
+            acc_range(chunk_off[c], chunk_off[c + 1] - chunk_off[c], s_comm);
+            acc_comm_busy = true;
+        }
+        if (acc_k && acc_k < acc_steps) return;
         if (early_on) {
-            sgd_chunk(c);
+            sgd_chunk(c, fanned);
             return;
         }
         if (clip_live && !(comm && overlap)) {  // the chunk's partials beside the rest of the backward
-            chunk_fan_in(c);
+            if (!fanned) chunk_fan_in(c);
             clip_partials(c, s_comm);
             clip_comm_busy = true;
             return;
         }
         if (!comm || !overlap) return;
-        chunk_fan_in(c);
+        if (!fanned) chunk_fan_in(c);
         const long long o = chunk_off[c], n = chunk_off[c + 1] - chunk_off[c];
         ncclResult_t r = ncclAllReduce(grads + o, grads + o, (size_t)n, ncclFloat32, ncclSum, comm, s_comm);
         if (r != ncclSuccess) set_error("ncclAllReduce(chunk %d): %s", c, ncclGetErrorString(r));
@@ -2520,15 +2576,31 @@ int vit_trainer_backward(vit_trainer_t* h) {
         return 1;
     }
     t.clip_parts_valid = false;
-    t.clip_live = t.clip_on() && !t.early_on && t.clip_overlap_on();
+    // gradient accumulation: this is backward acc_k of its window; only the one that completes it (or any
+    // backward while accumulation is off) has consumers in chunk_done
+    t.acc_k = t.acc_next();
+    const bool final_bwd = t.acc_k == 0 || t.acc_k == t.acc_steps;
+    if (t.acc_k && !t.ensure_arena(t.acc, false)) return 1;
+    t.clip_live = t.clip_on() && !t.early_on && t.clip_overlap_on() && final_bwd;
+    t.acc_chunked = t.acc_k && (t.acc_overlap_on() ||
+                                (final_bwd && (t.early_on || t.clip_live || (t.comm && t.overlap))));
     if (t.lowp()) t.backward_bf16(); else t.backward_f32();
+    if (t.acc_k && !t.acc_chunked) t.acc_range(0, t.arena_elems, t.s);  // the plain form: every writer has joined s
+    if (t.acc_comm_busy) {  // s, and through it every later writer and reader of either arena, behind the sums
+        t.order(t.comm_done, t.s_comm, t.s);
+        t.acc_comm_busy = false;
+    }
+    if (t.acc_k && !vit::has_error()) t.acc_done = t.acc_k;
+    t.acc_k = 0;
+    t.acc_chunked = false;
     t.clip_parts_valid = t.clip_live && !vit::has_error();
     t.clip_live = false;
     return vit::has_error();
 }
 int vit_trainer_step(vit_trainer_t* h, float lr) {
-    if (!h->t.ema_unlocked("vit_trainer_step")) return 1;
+    if (!h->t.ema_unlocked("vit_trainer_step") || !h->t.acc_closed("vit_trainer_step")) return 1;
     h->t.step(lr);
+    h->t.acc_done = 0;
     return vit::has_error();
 }
 int vit_trainer_train_step(vit_trainer_t* h, float lr, int b_global) {
@@ -2538,14 +2610,51 @@ int vit_trainer_train_step(vit_trainer_t* h, float lr, int b_global) {
     vit_trainer_forward(h, b_global);
     // the fused step knows lr before the backward: SGD per finished chunk (Trainer::early_sgd)
     // (not under gradient clipping: no parameter may change before the global norm exists)
+    // (under gradient accumulation only in the call that completes a window: the others update nothing)
+    const int k = t.acc_next();
+    const bool closes = k == 0 || k == t.acc_steps;
     t.early_on = t.early_sgd_on() && t.lowp() && !t.comm && t.two_streams && !t.timing && t.s2 && t.has_targets &&
-                 !t.clip_on();
+                 !t.clip_on() && closes;
     t.early_lr = lr;
     if (t.early_on && t.sgdm_on() && !t.ensure_sgd_buf()) t.early_on = false;  // (the error is set: step() reports it)
     vit_trainer_backward(h);
     t.early_done = t.early_on && !vit::has_error();
     t.early_on = false;
+    if (!closes) return vit::has_error();  // a micro-step inside the window: accumulated, no update
     vit_trainer_step(h, lr);
+    return vit::has_error();
+}
+int vit_trainer_set_grad_accum(vit_trainer_t* h, int steps) {
+    if (!h || steps < 1) {
+        set_error("vit_trainer_set_grad_accum: %s", h ? "steps must be >= 1" : "null trainer");
+        return 1;
+    }
+    auto& t = h->t;
+    VIT_HIP(hipDeviceSynchronize());  // the sums in flight read the count
+    t.acc_steps = steps;
+    t.acc_done = 0;  // any call abandons an open window
+    return vit::has_error();
+}
+int vit_trainer_get_grad_accum_info(vit_trainer_t* h, int* steps, int* done) {
+    if (!h) {
+        set_error("vit_trainer_get_grad_accum_info: null trainer");
+        return 1;
+    }
+    if (steps) *steps = h->t.acc_steps;
+    if (done) *done = h->t.acc_done;
+    return 0;
+}
+int vit_trainer_get_grad_accum(vit_trainer_t* h, float* host) {
+    if (!h || !host) {
+        set_error("vit_trainer_get_grad_accum: null argument");
+        return 1;
+    }
+    auto& t = h->t;
+    if (!t.acc_open()) {
+        set_error("vit_trainer_get_grad_accum: no open window (micro-step %d of %d)", t.acc_done, t.acc_steps);
+        return 1;
+    }
+    t.device_to_canon(t.acc, host);  // on s, which every backward leaves behind its sums
     return vit::has_error();
 }
 int vit_trainer_set_batch_jpeg(vit_trainer_t* h, vit_jpeg_loader_t* l, const float* mean3, const float* std3) {
@@ -2574,8 +2683,9 @@ int vit_trainer_set_augment_plan(vit_trainer_t* h, const vit_aug_op_t* host_plan
 }
 int vit_trainer_step_adamw(vit_trainer_t* h, float lr, float beta1, float beta2, float eps,
                            float weight_decay) {
-    if (!h->t.ema_unlocked("vit_trainer_step_adamw")) return 1;
+    if (!h->t.ema_unlocked("vit_trainer_step_adamw") || !h->t.acc_closed("vit_trainer_step_adamw")) return 1;
     h->t.step_adamw(lr, vit_adamw_t{beta1, beta2, eps, weight_decay});
+    h->t.acc_done = 0;
     return vit::has_error();
 }
 int vit_trainer_step_lamb(vit_trainer_t* h, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -2584,7 +2694,7 @@ int vit_trainer_step_lamb(vit_trainer_t* h, float lr, float beta1, float beta2, 
         set_error("vit_trainer_step_lamb: null trainer");
         return 1;
     }
-    if (!h->t.ema_unlocked("vit_trainer_step_lamb")) return 1;
+    if (!h->t.ema_unlocked("vit_trainer_step_lamb") || !h->t.acc_closed("vit_trainer_step_lamb")) return 1;
     if (!(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f)) {
         set_error("vit_trainer_step_lamb: beta1 %g / beta2 %g outside [0, 1)", (double)beta1, (double)beta2);
         return 1;
@@ -2599,6 +2709,7 @@ int vit_trainer_step_lamb(vit_trainer_t* h, float lr, float beta1, float beta2, 
         return 1;
     }
     h->t.step_lamb(lr, vit_adamw_t{beta1, beta2, eps, weight_decay}, flags);
+    h->t.acc_done = 0;
     return vit::has_error();
 }
 int vit_trainer_get_lamb_info(vit_trainer_t* h, float* w_norm, float* u_norm, float* ratio, long long* steps) {
@@ -2778,7 +2889,7 @@ int vit_trainer_eval(vit_trainer_t* h, int* host_pred, int* host_correct) {
 int vit_trainer_save_checkpoint(vit_trainer_t* h, const char* path) {
     using namespace vit::ckpt;
     auto& t = h->t;
-    if (!t.ema_unlocked("vit_trainer_save_checkpoint")) return 1;
+    if (!t.ema_unlocked("vit_trainer_save_checkpoint") || !t.acc_closed("vit_trainer_save_checkpoint")) return 1;
     VIT_HIP(hipDeviceSynchronize());
     if (vit::has_error()) return 1;
     // the arenas that exist, in file order: params; m, v once an AdamW or LAMB step has run; the EMA while it
@@ -2829,6 +2940,7 @@ int vit_trainer_load_checkpoint(vit_trainer_t* h, const char* path) {
         if (r.read((Section)k, host[k].data())) return 1;
     }
     VIT_HIP(hipDeviceSynchronize());
+    t.acc_done = 0;  // an open accumulation window belongs to the parameters that are replaced here
     t.canon_to_device(host[SEC_PARAMS].data(), t.params);
     t.refresh_bf16();
     if (hd.has(SEC_M)) {
@@ -2977,6 +3089,8 @@ int vit_trainer_set_option(vit_trainer_t* h, const char* name, int value) {
         t.ema_fused = value != 0;
     } else if (n == "early_sgd") {  // one GPU: SGD per finished gradient chunk inside train_step (default: fp8 mode only)
         t.early_sgd = value < 0 ? -1 : value != 0;
+    } else if (n == "accum_overlap") {  // gradient accumulation: the sums per chunk beside the backward (1), one pass behind it (0), auto (-1)
+        t.acc_overlap = value < 0 ? -1 : value != 0;
     } else if (n == "clip_overlap") {  // gradient clipping: partial sums per chunk beside the backward (1), at step time (0), auto (-1)
         t.clip_overlap = value < 0 ? -1 : value != 0;
     } else if (n == "last_cls") {  // bf16: the last block's row-wise ops after attention on the CLS rows only (default 1)
